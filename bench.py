@@ -8,10 +8,17 @@ batch resident on the device) on the synthetic ~50k-cell cylinder mesh (BASELINE
 One process per GPU; every rank owns `--meshes-per-gpu` meshes (weak scaling, graphs sharded by rank) and
 the flat fp32 gradient (4.7 MB) is all-reduced with RCCL before the fused Adam step.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, picks the launch mode, times exactly K steps and prints the line; `--dump-outputs DIR` then
+also writes what the last timed step handed its caller as DIR/<name>.npy.  Every other leg below runs with `--full` only.
+
 What the line carries (DESIGN.md 5 explains every figure):
-  value / ms_per_step   K-step timed loops bracketed by barrier + synchronize, repeated until `--min-time` seconds have
-                        been timed (so the device is visibly busy); value = all timed steps / all timed seconds, no picking
+  value / ms_per_step   ONE K-step timed loop bracketed by barrier + synchronize (`--min-time S`: repeated until S seconds
+                        have been timed); value = all timed steps / all timed seconds, no picking
   step_modes            the same step timed as eager launches AND as hipGraph replay (the faster one runs the timed loops)
+  --full only:
+  allreduce_exposed_us  (several ranks) the step with the gradient exchange minus the same step without it
+  drop_in               the reference driver's own call sequence on NNmodel, beside the fused step
+  fp32 / f16 / bf16     the same step with the other forms of the GEMM products
   roofline              the dominant kernel, measured live with HIP events around every launch (single stream, eager)
   roofline_kernels      every kernel class of the step (chains, weight gradients, segmented reduce, slice attention,
                         finite-volume, reductions, weight images, input preparation / Adam) with algorithmic flops / bytes
@@ -212,6 +219,34 @@ def drop_in_leg(device, graphs_cpu, ts_ms, steps, min_time=1.0):
     return out
 
 
+DUMP_MAX_ELEMENTS = 1 << 21   # per array (8 MB of float32): eight arrays stay under 64 MB whatever the mesh size
+
+
+def dump_outputs(out_dir, ts):
+    """What the timed path handed its caller after its LAST timed step, as float32 DIR/<name>.npy: the scalar loss and the
+    per-graph residual losses, the predicted node / cell fields, and the state the step left (parameters, their gradients,
+    Adam's two moments; every tensor without the alignment padding between them, in state_dict order).  An array longer than
+    DUMP_MAX_ELEMENTS is reduced to a fixed, seeded sample of its flattened elements (same indices for the same size)."""
+    torch.cuda.synchronize()
+    G = ts.G
+    names = list(G.off)
+
+    def flat(buf, keep):
+        return torch.cat([buf[G.off[n]:G.off[n] + G.numel(n)] for n in names if keep(n)])
+    arrays = {"loss": ts.loss, "residual_losses": ts.losses, "uvp_node": ts.uvp_node, "uvp_cell": ts.uvp_cell,
+              "params": flat(ts.flat_p, lambda n: True), "grads": flat(ts.flat_g, lambda n: n not in G.skip),
+              "adam_exp_avg": flat(ts.flat_m, lambda n: True), "adam_exp_avg_sq": flat(ts.flat_v, lambda n: True)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def self_launch_command(gpus, argv, port=None):
     """The command `python bench.py --gpus N ...` runs when it is started WITHOUT a launcher: the driver's own multi-GPU line
     (one rank per GPU over RCCL, rendezvous on 127.0.0.1), with this invocation's arguments passed through unchanged."""
@@ -249,8 +284,16 @@ def main():
     ap.add_argument("--graph", choices=("auto", "on", "off", "list"), default="auto",
                     help="how the step is launched: off = eager Python launches, on = hipGraph replay, list = command-list "
                          "replay (gfv/cmdlist.py); auto = time all three (reported as step_modes) and keep the fastest")
-    ap.add_argument("--min-time", type=float, default=2.0,
-                    help="repeat the timed K-step loop until this many seconds have been timed (0: exactly one loop)")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the timed K-step loop until this many seconds have been timed (0, the default: exactly one "
+                         "loop of --steps steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: the exposed all-reduce, the drop-in call sequence, the "
+                         "roofline profile and copy rate, the fp32 / f16 / bf16 product forms and the CPU baseline (the "
+                         "options below that tune those legs act with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step handed its caller (loss, residual losses, "
+                         "predicted fields, parameters, gradients, Adam moments) as DIR/<name>.npy (float32)")
     ap.add_argument("--cpu-budget", type=float, default=45.0, help="seconds of CPU work for the cpu_baseline leg (0 = skip)")
     ap.add_argument("--profile-steps", type=int, default=3)
     ap.add_argument("--skip-fp32-form", action="store_true",
@@ -405,10 +448,12 @@ def main():
         t[rank] = rank_ms[0]
         dist.all_reduce(t)
         rank_ms = [float(v) for v in t.tolist()]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ts)
     # what the gradient exchange costs the step: the same step, same launch mode, with the collectives taken out (every rank
     # then steps on its own gradient: a timing leg, so the replicas' state is put back afterwards)
     exposed_us = None
-    if dist_on:
+    if dist_on and args.full:
         snap = [b.clone() for b in (ts.flat_p, ts.flat_m, ts.flat_v, ts.adam_state)]
         ts.dist_on = ts.engine.dist_force = False
         for _ in range(6):
@@ -424,7 +469,7 @@ def main():
 
     # ---- the drop-in path: the reference driver's literal call sequence on the same batch, beside the fused TrainStep ----
     drop_in = None
-    if rank == 0 and world == 1 and not args.skip_drop_in:
+    if args.full and rank == 0 and world == 1 and not args.skip_drop_in:
         drop_in = drop_in_leg(device, graphs_cpu, ms_per_step, max(5, min(20, args.steps)))
 
     # ---- roofline leg: same step, eager, HIP events around every launch --------------------------------------------
@@ -432,8 +477,8 @@ def main():
     # above runs the weight-gradient kernels on a side stream, concurrently with the dX chains; here every kernel is
     # launched on ONE stream so that its duration is its own (concurrent kernels share the CUs and stretch each other).
     roof, roof_all = None, []
-    copy_rate = measured_copy_rate_gbs(device) if (rank == 0 and not args.skip_copy_rate) else 0.0
-    do_roofline = args.profile_steps > 0   # (--profile-steps 0: a profiling run that executes the timed form of the step only)
+    copy_rate = measured_copy_rate_gbs(device) if (args.full and rank == 0 and not args.skip_copy_rate) else 0.0
+    do_roofline = args.full and args.profile_steps > 0   # (--profile-steps 0: a profiling run that executes the timed form only)
     single_stream_ms = float("nan")
     if do_roofline:
         ts_use_graph, eng_overlap = ts.use_graph, ts.engine.overlap
@@ -570,7 +615,7 @@ def main():
 
     # ---- the same step with every GEMM product on the fp32 MFMA (the form without the fp16 split), for the record ----
     fp32_form = None
-    if ts.engine.f16split and not args.skip_fp32_form:
+    if args.full and ts.engine.f16split and not args.skip_fp32_form:
         ts_use_graph = ts.use_graph
         ts.engine.f16split = False      # (same launch mode as `value`: a form change re-records the list, Engine.capture_signature)
         lib.gfv_set_f16split(0)
@@ -586,7 +631,7 @@ def main():
     # ---- and with ONE fp16 x fp16 product per term (the reduced-precision form, include/gfv.h gfv_set_f16split(2)): the
     # counterpart of the reference's autocast runs (BASELINE configs 3 / 5), reported beside the headline, never as it ----
     f16_form = None
-    if ts.engine.f16split and not args.skip_fp32_form:
+    if args.full and ts.engine.f16split and not args.skip_fp32_form:
         ts_use_graph = ts.use_graph
         lib.gfv_set_f16split(2)
         for _ in range(5):
@@ -607,7 +652,7 @@ def main():
     # ---- and on bf16 operands (gfv_set_f16split(3): v_mfma_f32_16x16x32_bf16 - BASELINE config 3's "bf16 MLP GEMMs on MFMA"
     # to the letter; same kernels, bf16-rounded operands, fp32 accumulation and fp32 everywhere else) ----
     bf16_form = None
-    if ts.engine.f16split and not args.skip_fp32_form:
+    if args.full and ts.engine.f16split and not args.skip_fp32_form:
         ts_use_graph = ts.use_graph
         lib.gfv_set_f16split(3)
         for _ in range(5):
@@ -627,7 +672,7 @@ def main():
 
     cpu = None
     gfv_host.restore(pinned_prev)   # the CPU baseline's intra-op threads (created now) go wherever the scheduler puts them
-    if rank == 0 and world == 1 and args.cpu_budget > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_budget > 0:
         # 16 threads is the fastest setting for this launch-bound eager workload on the GPU box's host
         # (measured 8/16/32/64/256 threads: 4.3 / 3.5 / 3.6 / 5.2 / 188 s per step); override with GFV_CPU_THREADS
         total = os.cpu_count() or 1
@@ -672,6 +717,7 @@ def main():
             "timed": {"loops": len(reps), "steps_per_loop": args.steps, "timed_steps": timed_steps,
                       "timed_seconds": round(elapsed, 4), "min_time": args.min_time,
                       "loop_ms_per_step_min_max": [round(1e3 * min(reps) / args.steps, 4), round(1e3 * max(reps) / args.steps, 4)]},
+            "full": args.full,   # False: the legs below that --full adds are null
             "step_modes": {k + "_ms_per_step": round(1e3 * v, 4) for k, v in modes.items()} | {"used": used},
             "dtype_note": ("fp32 values end to end; the products of the fused GEMM chains run as 3 f16 MFMAs on exact (hi, lo) "
                            "fp16 splits of the fp32 operands with fp32 accumulation (error <= the f32 MFMA's, parity tests at 1e-5)"
@@ -713,8 +759,9 @@ def main():
             # reference algorithm vs what the launches execute (EdgeBlock first layer factored through
             # the nodes, gfv/engine.py): the fraction of the fp32 MFMA peak is quoted on the EXECUTED flops
             "algorithmic_step_tflops": round(algorithmic_step_flops(sz) / 1e12, 4),
-            "executed_step_tflops": round(executed_flops / 1e12, 4),
-            "step_mfma_frac": round(executed_flops / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
+            "executed_step_tflops": round(executed_flops / 1e12, 4) if do_roofline else None,
+            "step_mfma_frac": (round(executed_flops / (ms_per_step * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4)
+                               if do_roofline else None),
             "roofline_note": ("per-kernel durations: HIP events around every launch, ONE stream, eager (profile leg); value: "
                               + {"eager": "eager launches from Python", "hip_graph": "hipGraph replay",
                                  "cmd_list": "command-list replay of the eager launch sequence (gfv/cmdlist.py)"}[used]

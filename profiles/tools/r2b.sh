@@ -6,7 +6,7 @@ timeout 1800 python -m pytest tests -m gpu -x -q > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
 for prio in 0 10; do
-GFV_SIDE_PRIO=$prio timeout 600 python3 $R/bench.py --cpu-budget 0 > $O/bench_prio$prio.json 2> $O/bench_prio$prio.err
+GFV_SIDE_PRIO=$prio timeout 600 python3 $R/bench.py --full --min-time 2 --cpu-budget 0 > $O/bench_prio$prio.json 2> $O/bench_prio$prio.err
 done
 tail -5 $O/pytest.log
 for prio in 0 10; do python3 -c "

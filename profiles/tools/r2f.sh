@@ -6,7 +6,7 @@ export GFV_PARITY_REPORT=$O/parity_fp64.txt
 timeout 2400 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python3 $R/bench.py --cpu-budget 0 --min-time 1.0 > $O/bench.json 2> $O/bench.err
+timeout 600 python3 $R/bench.py --full --cpu-budget 0 --min-time 1.0 > $O/bench.json 2> $O/bench.err
 grep -E "passed|failed|FAILED|RCCLDIFF|RCCLRESULT" $O/pytest.log | head -40
 grep -E "^E  " $O/pytest.log | head -40
 python3 -c "

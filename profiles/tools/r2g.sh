@@ -5,8 +5,8 @@ cd $R
 timeout 2400 python -m pytest tests -m gpu -q -x > $O/pytest.log 2>&1
 echo "pytest rc=$?" >> $O/pytest.log
 cd /tmp && export TMPDIR=/tmp
-timeout 600 python3 $R/bench.py --cpu-budget 0 --min-time 1.0 > $O/bench.json 2> $O/bench.err
-GFV_CSR_FUSE=0 timeout 600 python3 $R/bench.py --cpu-budget 0 --min-time 1.0 > $O/bench_nofuse.json 2> $O/bench_nofuse.err
+timeout 600 python3 $R/bench.py --full --cpu-budget 0 --min-time 1.0 > $O/bench.json 2> $O/bench.err
+GFV_CSR_FUSE=0 timeout 600 python3 $R/bench.py --full --cpu-budget 0 --min-time 1.0 > $O/bench_nofuse.json 2> $O/bench_nofuse.err
 grep -E "passed|failed|FAILED" $O/pytest.log | head -40
 grep -E "^E  " $O/pytest.log | head -30
 for f in bench bench_nofuse; do python3 -c "

@@ -75,11 +75,39 @@ def int_fingerprint(a):
     return np.array([a.shape[1], int(a[0].sum()), int(a[1].sum()), int(((a[0] * 31 + a[1] * 17 + pos) % 1000003).sum())], dtype=np.int64)
 
 
+class Fixture(dict):
+    """np.load's interface (fx[key], fx.files) over the arrays of a fixture kept in more than one .npz file."""
+    @property
+    def files(self):
+        return list(self)
+
+
+# the reference's outputs on a mesh: saved beside its inputs, in <stem>_expected.npz (every committed file stays under 1 MiB)
+EXPECTED_KEYS = ("loss", "loss_cont", "loss_mom_x", "loss_mom_y", "loss_press", "uvp_node", "uvp_cell", "grad_fp")
+
+
+def save_fixture(path, arrays):
+    """np.savez_compressed in two files: the inputs in `path`, EXPECTED_KEYS in <stem>_expected.npz."""
+    np.savez_compressed(path, **{k: v for k, v in arrays.items() if k not in EXPECTED_KEYS})
+    np.savez_compressed(path[:-len(".npz")] + "_expected.npz", **{k: v for k, v in arrays.items() if k in EXPECTED_KEYS})
+
+
+def load_fixture(path):
+    """The arrays of `path` and, where it exists, of <stem>_expected.npz (save_fixture) as one Fixture."""
+    fx = np.load(path)
+    out = Fixture((k, fx[k]) for k in fx.files)
+    extra = path[:-len(".npz")] + "_expected.npz"
+    if os.path.exists(extra):
+        fx = np.load(extra)
+        out.update((k, fx[k]) for k in fx.files)
+    return out
+
+
 def real_mesh(name, golden_dir=None, device=None):
     """One of REAL_MESHES -> (graphs, fixture, mesh dict).  device: prepare the stencil / moments with gfv.device_prep there."""
     import json
     golden_dir = golden_dir or os.path.dirname(os.path.abspath(__file__))
-    fx = np.load(os.path.join(golden_dir, name + ".npz"))
+    fx = load_fixture(os.path.join(golden_dir, name + ".npz"))
     raw = {k[4:]: (fx[k].astype(np.int64) if fx[k].dtype.kind == "i" else fx[k]) for k in fx.files
            if k.startswith("raw.") and k != "raw.bc"}
     raw["bc"] = json.loads(str(fx["raw.bc"]))
@@ -106,7 +134,7 @@ def poly_cylinder(golden_dir=None):
     import json
     from gfv import ingest
     golden_dir = golden_dir or os.path.dirname(os.path.abspath(__file__))
-    fx = np.load(os.path.join(golden_dir, "poly_cylinder.npz"))
+    fx = load_fixture(os.path.join(golden_dir, "poly_cylinder.npz"))
     tec = {"pos": fx["tec.pos"], "face_node": fx["tec.face_node"].astype(np.int64), "left": fx["tec.left"].astype(np.int64),
            "right": fx["tec.right"].astype(np.int64), "boundary_pos": fx["tec.boundary_pos"]}
     bcd = json.loads(str(fx["raw.bc"]))

@@ -236,7 +236,7 @@ def main():
                  "grad_fp": np.stack([cases.fingerprint(grads[k].numpy()) if grads[k] is not None else np.full(3, np.nan)
                                       for k in names])})
     out = os.path.join(HERE, "poly_cylinder.npz")
-    np.savez_compressed(out, **save)
+    cases.save_fixture(out, save)
     print("saved", os.path.getsize(out) / 1e6, "MB")
 
 

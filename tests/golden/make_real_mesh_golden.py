@@ -151,7 +151,7 @@ def generate(fixture):
                  "uvp_node": uvp_node.detach().numpy(), "uvp_cell": uvp_cell.detach().numpy(),
                  "grad_fp": np.stack([cases.fingerprint(grads[k].numpy()) if grads[k] is not None else np.full(3, np.nan)
                                       for k in names])})
-    np.savez_compressed(os.path.join(HERE, fixture + ".npz"), **save)
+    cases.save_fixture(os.path.join(HERE, fixture + ".npz"), save)
     print("saved", os.path.getsize(os.path.join(HERE, fixture + ".npz")) / 1e6, "MB")
 
 

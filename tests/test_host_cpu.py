@@ -256,10 +256,18 @@ def test_bench_starts_its_own_ranks_when_called_without_a_launcher(monkeypatch):
     assert "--nproc-per-node=2" in seen["cmd"] and seen["cmd"][-4:] == ["--gpus", "2", "--steps", "3"]
     assert seen["env"]["HSA_ENABLE_IPC_MODE_LEGACY"] == "0"
     # under a launcher (WORLD_SIZE set) the same invocation goes on as a rank: here it stops at the GPU check, not at a spawn
+    # (no device visible whatever the host has, so that check is the one reached; the rank pins the process's threads to one L3
+    # on its way there, which is undone so that later tests keep the CPUs they started with)
     seen.clear()
     monkeypatch.setenv("WORLD_SIZE", "2")
-    with pytest.raises(SystemExit) as ex:
-        bench.main()
+    monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 0)
+    affinity = os.sched_getaffinity(0) if hasattr(os, "sched_getaffinity") else None
+    try:
+        with pytest.raises(SystemExit) as ex:
+            bench.main()
+    finally:
+        if affinity is not None:
+            os.sched_setaffinity(0, affinity)
     assert not seen and "MI355X" in str(ex.value.code)
 
 
@@ -279,7 +287,9 @@ def test_host_thread_placement_helper(tmp_path):
     now = os.sched_getaffinity(0)
     assert now <= before and len(now) >= 1
     if prev is not None:
-        assert prev == before and now == (host.l3_group(os.sched_getcpu()) & before or now)
+        # (the CPU pin_to_l3 took the L3 of: the one it ran on where os.sched_getcpu exists, else the lowest allowed one)
+        cpu = os.sched_getcpu() if hasattr(os, "sched_getcpu") else min(before)
+        assert prev == before and now == (host.l3_group(cpu) & before or now)
     host.restore(prev)
     assert os.sched_getaffinity(0) == before
     groups = host.l3_groups(before)
