@@ -113,9 +113,19 @@ class NNmodel(nn.Module):
         accumulate = norm_global and self.node_norm.should_accumulate()
         names, tensors = self.param_names_tensors()
         tensors = pad_parameters(names, tensors, self.hidden_size)   # (hidden_size 128: as they are)
-        losses, uvp_node, uvp_cell, ea15 = GF.ModelFn.apply(
-            self.engine(), plan, names, self.node_norm.buffers_dict(), x,
-            dict(norm_global=norm_global, accumulate=accumulate), self._replay if self.hidden_size == 128 else None, *tensors)
+        if not torch.is_grad_enabled():
+            # nothing can ask for a gradient (torch.no_grad(): validation, running a trained model): the forward-only engine path -
+            # the same launches with nothing saved for a backward, issued eagerly and outside the replay cache (no recorded entry
+            # is left waiting for a backward that never comes).  gfv.rollout.Rollout is the fast way to run many such steps.
+            eng = self.engine()
+            P = dict(zip(names, (t.detach() for t in tensors)))
+            with eng.model_width():
+                losses, uvp_node, uvp_cell, ea15, _ = eng.forward(P, self.node_norm.buffers_dict(), x, plan, norm_global=norm_global,
+                                                                  accumulate=accumulate, keep=False)
+        else:
+            losses, uvp_node, uvp_cell, ea15 = GF.ModelFn.apply(
+                self.engine(), plan, names, self.node_norm.buffers_dict(), x,
+                dict(norm_global=norm_global, accumulate=accumulate), self._replay if self.hidden_size == 128 else None, *tensors)
         if accumulate:
             self.node_norm.note_accumulated()
         graph_node.norm_uvp = False

@@ -46,7 +46,9 @@ struct CtArgs {
   int M, hidden;
 };
 
-template <int LOWP>
+// SAVE = false: the forward-only form (fx1 == z == NULL) - the two saved tensors are not stored; nothing else differs (the
+// residual rows already stay in registers)
+template <int LOWP, bool SAVE>
 __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int* status) {
   constexpr bool BF = LOWP == 2;
   constexpr int TG = 2;
@@ -159,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
     const float si = sinv[q * 16 + j];
     fx[q][0] = (acc[q][0] * si) * invw + bA.x + rres[q].x; fx[q][1] = (acc[q][1] * si) * invw + bA.y + rres[q].y;
     fx[q][2] = (acc[q][2] * si) * invw + bA.z + rres[q].z; fx[q][3] = (acc[q][3] * si) * invw + bA.w + rres[q].w;
-    if (live) st4(A.fx1 + (size_t)row * 128 + c0, fx[q]);
+    if (SAVE && live) st4(A.fx1 + (size_t)row * 128 + c0, fx[q]);
     const float mw = row_sum((fx[q][0] + fx[q][1]) + (fx[q][2] + fx[q][3])) * (1.0f / 16.0f);   // this wave's 16 columns
     const float d0 = fx[q][0] - mw, d1 = fx[q][1] - mw, d2 = fx[q][2] - mw, d3 = fx[q][3] - mw;
     const float m2 = row_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
@@ -246,7 +248,7 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
       for (int n = 0; n < 2; ++n) {
         float zz[4] = {(zc[q][n][0] * isB) * invw + bB[n].x, (zc[q][n][1] * isB) * invw + bB[n].y,
                        (zc[q][n][2] * isB) * invw + bB[n].z, (zc[q][n][3] * isB) * invw + bB[n].w};
-        if (live) st4(A.z + (size_t)row * 256 + cz + 16 * n, zz);
+        if (SAVE && live) st4(A.z + (size_t)row * 256 + cz + 16 * n, zz);
         const gfv_f2 g01 = gfv_gelu2(gfv_f2{zz[0], zz[1]}), g23 = gfv_gelu2(gfv_f2{zz[2], zz[3]});
         mabs = fmaxf(mabs, live ? max3_abs(max3_abs(0.f, g01.x, g01.y), g23.x, g23.y) : 0.f);
         e8[4 * n + 0] = g01.x * CT_SH; e8[4 * n + 1] = g01.y * CT_SH; e8[4 * n + 2] = g23.x * CT_SH; e8[4 * n + 3] = g23.y * CT_SH;
@@ -701,8 +703,14 @@ int gfv_internal_ctrans_fwd_try(const gfv_trans_mlp_t* a, int form, hipStream_t 
            a->fx1, a->z, a->out, a->M, gfv_hidden_size()};
   int* st = gfv_internal_status_ptr();
   const dim3 grid((a->M + 31) / 32), blk(512);
-  if (form == 3) GFV_LAUNCH((ctrans_fwd_kernel<2>), grid, blk, 0, stream, B, st);
-  else if (form == 2) GFV_LAUNCH((ctrans_fwd_kernel<1>), grid, blk, 0, stream, B, st);
-  else GFV_LAUNCH((ctrans_fwd_kernel<0>), grid, blk, 0, stream, B, st);
+  if (a->fx1) {
+    if (form == 3) GFV_LAUNCH((ctrans_fwd_kernel<2, true>), grid, blk, 0, stream, B, st);
+    else if (form == 2) GFV_LAUNCH((ctrans_fwd_kernel<1, true>), grid, blk, 0, stream, B, st);
+    else GFV_LAUNCH((ctrans_fwd_kernel<0, true>), grid, blk, 0, stream, B, st);
+  } else {
+    if (form == 3) GFV_LAUNCH((ctrans_fwd_kernel<2, false>), grid, blk, 0, stream, B, st);
+    else if (form == 2) GFV_LAUNCH((ctrans_fwd_kernel<1, false>), grid, blk, 0, stream, B, st);
+    else GFV_LAUNCH((ctrans_fwd_kernel<0, false>), grid, blk, 0, stream, B, st);
+  }
   return 1;
 }

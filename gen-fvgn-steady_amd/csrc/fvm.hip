@@ -745,7 +745,7 @@ __global__ __launch_bounds__(1024) void fvm_tail_kernel(const float* __restrict_
   }
   if (tid == 0) {
     const float S0 = red[0][0], S1 = red[1][0], S2 = red[2][0], S3 = red[3][0];
-    sums[4 * b] = S0; sums[4 * b + 1] = S1; sums[4 * b + 2] = S2; sums[4 * b + 3] = S3;
+    if (sums) { sums[4 * b] = S0; sums[4 * b + 1] = S1; sums[4 * b + 2] = S2; sums[4 * b + 3] = S3; }   // (the backward's; NULL: forward only)
     losses[4 * b] = sqrtf(S0) * theta[(size_t)b * 9 + 1];
     losses[4 * b + 1] = sqrtf(S1) * sigma[(size_t)b * 3];
     losses[4 * b + 2] = sqrtf(S2) * sigma[(size_t)b * 3 + 1];
@@ -1244,7 +1244,7 @@ extern "C" int gfv_wlsq_moments(const double* pos, const int32_t* rowptr, const 
 extern "C" int gfv_fvm_fwd_tail(const gfv_fvm_mesh_t* m, const float* cres, const float* phic, const float* phi, float* sums,
                                 float* losses, float* uvp_node, const float* hyper, float* loss, float* gloss, int32_t* counter,
                                 void* stream) {
-  if (!m || m->B <= 0 || !cres || !sums || !losses) return GFV_ERR_ARG;
+  if (!m || m->B <= 0 || !cres || !losses) return GFV_ERR_ARG;
   if (hyper && (!loss || !gloss || !counter)) return GFV_ERR_ARG;
   if (uvp_node && (!phic || !phi)) return GFV_ERR_ARG;
   GfvProfScope ps_(GFV_K_FVM, 0, 16.0 * gfv_prof_size_Sigma() / 3.0 + (uvp_node ? 4.0 * gfv_prof_size_Sigma() + 68.0 * m->N : 0.0), stream);

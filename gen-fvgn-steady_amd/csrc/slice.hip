@@ -260,9 +260,9 @@ __global__ __launch_bounds__(256) void slice_attention_fwd_kernel(const AttnFwdA
   for (int idx = tid; idx < G * D; idx += 256) {
     const int g = idx / D, c = idx % D;
     const float t = sTok[g][c] / (sNrm[g] + 1e-5f);  // GraphTransolver.py:74
-    A.token[(size_t)bh * G * D + idx] = t;
+    if (A.token) A.token[(size_t)bh * G * D + idx] = t;   // (token / norm / attn: read by the backward only, NULL in a forward-only step)
   }
-  if (tid < G) A.norm[bh * G + tid] = sNrm[tid];
+  if (A.norm && tid < G) A.norm[bh * G + tid] = sNrm[tid];
   __syncthreads();
   for (int idx = tid; idx < G * D; idx += 256) {
     const int g = idx / D, c = idx % D;
@@ -297,7 +297,8 @@ __global__ __launch_bounds__(256) void slice_attention_fwd_kernel(const AttnFwdA
     for (int j = 0; j < G; ++j) sA[tid][j] *= inv;
   }
   __syncthreads();
-  for (int idx = tid; idx < G * G; idx += 256) A.attn[(size_t)bh * G * G + idx] = sA[idx / G][idx % G];
+  if (A.attn)
+    for (int idx = tid; idx < G * G; idx += 256) A.attn[(size_t)bh * G * G + idx] = sA[idx / G][idx % G];
   for (int idx = tid; idx < G * D; idx += 256) {
     const int i = idx / D, c = idx % D;
     float s = 0.f;

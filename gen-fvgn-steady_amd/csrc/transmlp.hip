@@ -104,7 +104,11 @@ struct TmFwdArgs {
   float ln_inv_n, ln_npad;
 };
 
-template <int LOWP>
+// SAVE = false: the forward-only form (gfv_trans_mlp_t.fx1 == z == NULL): z (1 KB per row) is not stored and no fx1 tensor exists -
+// the rows of fx1 the last residual adds are parked in the lane's own elements of `out`, which the same lane reads back and
+// overwrites at the end (the kernel sits at its 256-register budget: the 32 residual values per lane do not fit beside the 64
+// fragment registers of the 256-deep product).  The same products, sums and scales in the same order: bit-identical `out`.
+template <int LOWP, bool SAVE>
 __global__ __launch_bounds__(512, 2) void trans_mlp_fwd_kernel(const TmFwdArgs A, int* status) {
   constexpr bool BF = LOWP == 2;
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(512, 2) void trans_mlp_fwd_kernel(const TmFwdArgs A
       const float4 r = ld4(A.res + mr * 128 + col);
       h[nt][0] = (acc[0] * inv) * invw + b.x + r.x; h[nt][1] = (acc[1] * inv) * invw + b.y + r.y;
       h[nt][2] = (acc[2] * inv) * invw + b.z + r.z; h[nt][3] = (acc[3] * inv) * invw + b.w + r.w;
-      if (live) st4(A.fx1 + mr * 128 + col, h[nt]);
+      if (live) st4((SAVE ? A.fx1 : A.out) + mr * 128 + col, h[nt]);
     }
     {
       float sm = 0.f;
@@ -176,7 +180,7 @@ __global__ __launch_bounds__(512, 2) void trans_mlp_fwd_kernel(const TmFwdArgs A
           const int col = 128 * p + 16 * nt + 4 * g;
           const float4 b = A.bB ? ld4(A.bB + col) : make_float4(0.f, 0.f, 0.f, 0.f);
           float zz[4] = {(acc[0] * inv) * invw + b.x, (acc[1] * inv) * invw + b.y, (acc[2] * inv) * invw + b.z, (acc[3] * inv) * invw + b.w};
-          if (live) st4(A.z + mr * 256 + col, zz);
+          if (SAVE && live) st4(A.z + mr * 256 + col, zz);
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float a = gfv_gelu(zz[r]);
@@ -196,7 +200,8 @@ __global__ __launch_bounds__(512, 2) void trans_mlp_fwd_kernel(const TmFwdArgs A
       const floatx4 acc = tm_mma<8, LOWP>(img, 0, nt, lane, yh, yl);
       const int col = 16 * nt + 4 * g;
       const float4 b = A.bC ? ld4(A.bC + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-      const float4 r = ld4(A.fx1 + mr * 128 + col);
+      // (a dead lane - a row past M, clamped to the last row - reads what that row's owner may already have overwritten: its result is not stored)
+      const float4 r = ld4((SAVE ? A.fx1 : A.out) + mr * 128 + col);
       float o[4] = {(acc[0] * TM_SH_INV) * invw + b.x + r.x, (acc[1] * TM_SH_INV) * invw + b.y + r.y,
                     (acc[2] * TM_SH_INV) * invw + b.z + r.z, (acc[3] * TM_SH_INV) * invw + b.w + r.w};
       if (live) st4(A.out + mr * 128 + col, o);
@@ -421,9 +426,12 @@ extern "C" int gfv_trans_mlp_fwd(const gfv_trans_mlp_t* a, void* stream) {
   if (a->M == 0) return GFV_OK;
   const int form = gfv_f16split_enabled();
   if (form == 0) return GFV_ERR_ARG;   // split-fp16 forms only: the caller keeps the three single-layer launches in the fp32-MFMA form
-  const void* ptrs[] = {a->x, a->res, a->img_out, a->img_pre, a->img_post, a->gamma, a->beta, a->wmax, a->fx1, a->z, a->out};
+  const void* ptrs[] = {a->x, a->res, a->img_out, a->img_pre, a->img_post, a->gamma, a->beta, a->wmax, a->out};
   for (const void* p : ptrs)
     if (!p || !tm_al16(p)) return GFV_ERR_ARG;
+  // the two saved tensors: both given, or both NULL (the forward-only form - same kernel family, same bits in `out`)
+  const bool save = a->fx1 != nullptr;
+  if (save != (a->z != nullptr) || (save && (!tm_al16(a->fx1) || !tm_al16(a->z)))) return GFV_ERR_ARG;
   if (!gfv_internal_wimg_form_ok(a->wmax)) return GFV_ERR_ARG;   // (images of the other class of product form: wimg.hip)
   if ((a->b_out && !tm_al16(a->b_out)) || (a->b_pre && !tm_al16(a->b_pre)) || (a->b_post && !tm_al16(a->b_post))) return GFV_ERR_ARG;
   TmFwdArgs B{};
@@ -432,7 +440,8 @@ extern "C" int gfv_trans_mlp_fwd(const gfv_trans_mlp_t* a, void* stream) {
   B.fx1 = a->fx1; B.z = a->z; B.out = a->out; B.M = a->M;
   tm_ln(B.ln_inv_n, B.ln_npad);
   // three Linear layers' flops; rows read: out_x, fx_in, fx1 (re-read); written: fx1, z (256 wide), out
-  GfvProfScope ps_(GFV_K_LIN1, 2.0 * a->M * (128.0 * 128 + 2 * 128.0 * 256), 4.0 * a->M * (3 * 128.0 + 128 + 256 + 128), stream);
+  GfvProfScope ps_(GFV_K_LIN1, 2.0 * a->M * (128.0 * 128 + 2 * 128.0 * 256),
+                   4.0 * a->M * (save ? 3 * 128.0 + 128 + 256 + 128 : 2 * 128.0 + 128), stream);
   if (gfv_internal_ctrans_fwd_try(a, form, (hipStream_t)stream)) {   // short launches: one 32-row tile per workgroup
     GFV_CHECK_LAUNCH();
     return GFV_OK;
@@ -440,15 +449,21 @@ extern "C" int gfv_trans_mlp_fwd(const gfv_trans_mlp_t* a, void* stream) {
   int* st = gfv_internal_status_ptr();
   const int nblk = (a->M + 127) / 128;
   const dim3 grid(nblk), blk(512);
-#define TM_F(LP)                                                                                          \
+#define TM_F(LP, SV)                                                                                       \
   do {                                                                                                    \
     static std::atomic<unsigned long long> done{0};                                                       \
-    if (!tm_dyn_lds(reinterpret_cast<const void*>(&trans_mlp_fwd_kernel<LP>), done)) return GFV_ERR_LAUNCH; \
-    GFV_LAUNCH((trans_mlp_fwd_kernel<LP>), grid, blk, 131072, (hipStream_t)stream, B, st);               \
+    if (!tm_dyn_lds(reinterpret_cast<const void*>(&trans_mlp_fwd_kernel<LP, SV>), done)) return GFV_ERR_LAUNCH; \
+    GFV_LAUNCH((trans_mlp_fwd_kernel<LP, SV>), grid, blk, 131072, (hipStream_t)stream, B, st);               \
   } while (0)
-  if (form == 3) TM_F(2);
-  else if (form == 2) TM_F(1);
-  else TM_F(0);
+  if (save) {
+    if (form == 3) TM_F(2, true);
+    else if (form == 2) TM_F(1, true);
+    else TM_F(0, true);
+  } else {
+    if (form == 3) TM_F(2, false);
+    else if (form == 2) TM_F(1, false);
+    else TM_F(0, false);
+  }
 #undef TM_F
   GFV_CHECK_LAUNCH();
   return GFV_OK;

@@ -349,6 +349,30 @@ class Engine:
         wi.build()
         return ops.set_weight_images(wi)
 
+    def build_static_images(self, P):
+        """Forward weight images of a parameter set whose VALUES stay as they are (a trained model that is being run, not trained):
+        the maximum and every known image built now, on the calling stream, and left valid.  The first forward after it still adds
+        the images of launches it has not seen (each built on the spot from the same maximum)."""
+        if not self.f16split:
+            return
+        prev = self._wi_enter("fwd", P)
+        ops.set_weight_images(prev)
+
+    def _wi_static_enter(self, P):
+        """The forward image set as `build_static_images` (or any forward since) left it: nothing is launched.  A training forward
+        of the same engine in between invalidates the set on its way out (`_wi_exit`) without touching the images' contents -
+        rebuilt here (same values -> same bits); the set belonging to another parameter set is an error."""
+        if not self.f16split:
+            return None
+        if self._wi is None or self._wi_key != self._pkey(P, fresh=True):
+            raise RuntimeError("static weight images belong to another parameter set: call build_static_images(P) first")
+        wi = self._wi["fwd"]
+        if len(wi.valid) != len(wi.images) and cmdlist.active() is None:
+            L.check(L.load().gfv_weight_absmax(self._wi_abs[0].data_ptr(), self._wi_abs[1], self._wmax.data_ptr(),
+                                               L.stream_ptr()), "gfv_weight_absmax")
+            wi.build()
+        return ops.set_weight_images(wi)
+
     def capture_signature(self):
         """Identity of everything a captured step points at inside the engine (weight images, descriptor tables,
         transposed copies); TrainStep drops its hipGraphs when it changes."""
@@ -439,7 +463,11 @@ class Engine:
         """w1: column block of the first weight that multiplies `segs` (default: all of it); padd = (t [*,256], s, r):
         gathered addend t[s[m], :128] + t[r[m], 128:] to the first pre-activation (factored EdgeBlock).
         nores_from_saved: the caller can form the output without the residual from what the launch saves anyway (pre-LayerNorm
-        rows + row statistics): where both exist the second output is not written and None is returned for it."""
+        rows + row statistics): where both exist the second output is not written and None is returned for it.
+        keep=False (forward-only step): nothing is saved for a backward - z1, z2 are NULL, and the pre-LayerNorm rows + statistics
+        exist only where the caller forms the residual-free output from them, i.e. exactly where a saving launch would have left
+        them for it (so that both forms run the same launches on the same kernel family: the family never looks at the save
+        pointers)."""
         names = self._mlp_names(prefix, ln)
         W1, b1, W2, b2, W3, b3 = (P[n] for n in names[:6])
         if w1 is not None:
@@ -447,16 +475,26 @@ class Engine:
         dev = W1.device
         nout = W3.shape[0]
         # (mean, 1 / std) of the LayerNorm rows for a backward launch that fuses the weight gradients (it does not recompute them)
-        fused_bwd = (keep and ln and self.fuse_dw and self.f16split and self.hidden == 128 and nout == 128
-                     and M >= self._fuse_dw_min and M > self._cbwd_max
-                     and (self._fuse_noout or all(sg.width % 32 == 0 for sg in segs)))
+        would_fuse = (ln and self.fuse_dw and self.f16split and self.hidden == 128 and nout == 128
+                      and M >= self._fuse_dw_min and M > self._cbwd_max
+                      and (self._fuse_noout or all(sg.width % 32 == 0 for sg in segs)))
+        fused_bwd = keep and would_fuse
         # (the small-tile backward reads them as well)
-        stats = _empty(dev, M, 2) if (fused_bwd or (keep and ln and self.f16split and nout == 128 and M <= self._cbwd_max)) else None
+        would_stats = would_fuse or (ln and self.f16split and nout == 128 and M <= self._cbwd_max)
         # that launch rebuilds z2 and the LayerNorm input from z1 (recompute form): they are not written here at all
         lean = fused_bwd and self.recompute
-        z1 = _empty(dev, M, 128) if keep else None
-        z2 = _empty(dev, M, 128) if (keep and not lean) else None
-        y3 = _empty(dev, M, 128) if (keep and ln and not lean) else None
+        if keep:
+            stats = _empty(dev, M, 2) if would_stats else None
+            z1 = _empty(dev, M, 128)
+            z2 = _empty(dev, M, 128) if not lean else None
+            y3 = _empty(dev, M, 128) if (ln and not lean) else None
+        else:
+            # forward only: the rows + statistics the aggregation reads, where the saving form would hand it those
+            from_saved = (want_nores and nores_from_saved and would_stats and ln and nout == 128
+                          and not (would_fuse and self.recompute))
+            z1 = z2 = None
+            y3 = _empty(dev, M, 128) if from_saved else None
+            stats = _empty(dev, M, 2) if from_saved else None
         out = _empty(dev, M, nout)
         if want_nores and nores_from_saved and y3 is not None and stats is not None and nout == 128:
             want_nores = False
@@ -468,6 +506,8 @@ class Engine:
             fin_gamma=P[names[6]] if ln else None, fin_beta=P[names[7]] if ln else None, fin_presave=y3,
             res=[res] if res is not None else None, out_nores=nores, fin_stats=stats,
             **(dict(padd=padd[0], padd_s=padd[1], padd_r=padd[2]) if padd is not None else {}))
+        if not keep:
+            return out, nores, dict(y3=y3, stats=stats)
         # (a segmented-sum input segment is kept for the backward in its assembled form, written by the launch itself)
         saved = dict(z1=z1, z2=z2, y3=y3, segs=segs if saved_segs is None else saved_segs, in_add=in_add, M=M, ln=ln,
                      prefix=prefix, stats=stats, lean=lean, fused=fused_bwd)
@@ -689,7 +729,9 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # GnBlock (EPD.py:177-195, blocks.py)
     # ------------------------------------------------------------------------------------------------------------
-    def gn_fwd(self, P, prefix, x, e, pl):
+    def gn_fwd(self, P, prefix, x, e, pl, keep=True):
+        """keep=False: forward only - the assembled neighbour sums are not written out where the launch forms them itself, the
+        MLPs save nothing, None comes back for the saved state."""
         N, E = pl.N, pl.E
         fuse = self.csr_fuse
         if self.factor:
@@ -699,7 +741,7 @@ class Engine:
             # of ~6 us instead of two of 5 + 8)
             if fuse and ((self._fuse_mask & 1) or N <= self._csr1_max) and ops.stack_ready(W1[:, 0:128], W1[:, 128:256], rows=True):
                 # nb = sum over the neighbours (blocks.py:84-99) formed in the prologue of the launch that multiplies it
-                nb = _empty(x.device, N, 128)
+                nb = _empty(x.device, N, 128) if keep else None
                 ops.rowtile_chain(N, [Seg(x, csr=(pl.n_rowptr, pl.n_col_node), save=nb)],
                                   [LayerSpec(W1[:, 0:128], stack=W1[:, 128:256])], [(pab, 256), (pab.data_ptr() + 512, 256)])
             else:
@@ -707,12 +749,12 @@ class Engine:
                 ops.rowtile_chain(N, [Seg(nb)], [LayerSpec(W1[:, 0:128], stack=W1[:, 128:256])],
                                   [(pab, 256), (pab.data_ptr() + 512, 256)])
             e_out, e_new, sv_e = self.mlp3_fwd(P, f"{prefix}.eb_module.net", E, [Seg(e)], res=e, want_nores=True,
-                                               w1=W1[:, 256:384], padd=(pab, pl.es, pl.er), nores_from_saved=self._agg_ln)
+                                               w1=W1[:, 256:384], padd=(pab, pl.es, pl.er), nores_from_saved=self._agg_ln, keep=keep)
             sv_e["nb"] = nb
         else:
             nb = ops.seg_gather_sum(x, pl.n_rowptr, pl.n_col_node, N)
             e_out, e_new, sv_e = self.mlp3_fwd(P, f"{prefix}.eb_module.net", E, [Seg(nb, pl.es), Seg(nb, pl.er), Seg(e)],
-                                               res=e, want_nores=True, nores_from_saved=self._agg_ln)
+                                               res=e, want_nores=True, nores_from_saved=self._agg_ln, keep=keep)
         if e_new is None:
             # (the aggregation of blocks.py:35-42 over LayerNorm(y3), formed on the way in from the rows and statistics the launch saved)
             ln_names = self._mlp_names(f"{prefix}.eb_module.net", True)
@@ -722,13 +764,15 @@ class Engine:
         if fuse and (self._fuse_mask & 2):
             # nbm = mean over the neighbours of the aggregates (blocks.py:44-51), in the node MLP's prologue; the launch
             # leaves the assembled rows ([N,128] buffer, columns 0:64) for the weight gradient of the first layer
-            nbm = _empty(x.device, N, 128)
+            nbm = _empty(x.device, N, 128) if keep else None
             x_out, _, sv_n = self.mlp3_fwd(P, f"{prefix}.nb_module.net", N,
                                            [Seg(agg, csr=(pl.n_rowptr, pl.n_col_node), scale=pl.inv_deg, save=nbm), Seg(x)],
-                                           res=x, saved_segs=[Seg(nbm, width=64, ld=128), Seg(x)])
+                                           res=x, saved_segs=[Seg(nbm, width=64, ld=128), Seg(x)] if keep else None, keep=keep)
         else:
             nbm = ops.seg_gather_sum(agg, pl.n_rowptr, pl.n_col_node, N, scale=pl.inv_deg)
-            x_out, _, sv_n = self.mlp3_fwd(P, f"{prefix}.nb_module.net", N, [Seg(nbm), Seg(x)], res=x)
+            x_out, _, sv_n = self.mlp3_fwd(P, f"{prefix}.nb_module.net", N, [Seg(nbm), Seg(x)], res=x, keep=keep)
+        if not keep:
+            return x_out, e_out, None
         return x_out, e_out, dict(sv_e=sv_e, sv_n=sv_n, prefix=prefix)
 
     def _edge_tmp(self, dev):
@@ -889,7 +933,11 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # Transolver block (GraphTransolver.py:48-95,163-169)
     # ------------------------------------------------------------------------------------------------------------
-    def trans_fwd(self, P, prefix, xg, emb, pl):
+    def trans_fwd(self, P, prefix, xg, emb, pl, keep=True):
+        """keep=False: forward only.  Still written, because a later launch of this forward reads them: fx_in (the residual of
+        to_out), fx_mid / x_mid (slice softmax + tokens), w (de-slice), out_token, out_x.  Not written: the attention's token /
+        norm / attn and the row-local chain's fx1 / z (its forward-only instantiation: the residual rows stay in registers in the
+        small-tile form and are parked in the lane's own elements of `out` in the 128-row-block form, csrc/transmlp.hip)."""
         lib = L.load()
         st = L.stream_ptr()
         N, B = pl.N, pl.B
@@ -917,21 +965,28 @@ class Engine:
             L.check(lib.gfv_slice_token_partial(w.data_ptr(), fx_mid.data_ptr(), pl.chunk_beg.data_ptr(),
                                                 pl.chunk_end.data_ptr(), pl.n_chunks, partial.data_ptr(), st), "token_partial")
         partial, gptr = self._graph_partials(partial, pl)
-        token, norm = _empty(dev, B, 8, 32, 16), _empty(dev, B, 8, 32)
-        attn, out_token = _empty(dev, B, 8, 32, 32), _empty(dev, B, 8, 32, 16)
+        token, norm = (_empty(dev, B, 8, 32, 16), _empty(dev, B, 8, 32)) if keep else (None, None)
+        attn, out_token = _empty(dev, B, 8, 32, 32) if keep else None, _empty(dev, B, 8, 32, 16)
         L.check(lib.gfv_slice_attention_fwd(partial.data_ptr(), gptr.data_ptr(), B, P[f"{a}.to_q.weight"].data_ptr(),
                                             P[f"{a}.to_k.weight"].data_ptr(), P[f"{a}.to_v.weight"].data_ptr(),
-                                            token.data_ptr(), norm.data_ptr(), attn.data_ptr(), out_token.data_ptr(), st),
+                                            L.ptr(token), L.ptr(norm), L.ptr(attn), out_token.data_ptr(), st),
                 "slice_attention_fwd")
+        if not keep:
+            del partial, fx_mid, x_mid
         out_x = _empty(dev, N, 128)
         L.check(lib.gfv_deslice(w.data_ptr(), out_token.data_ptr(), pl.batch.data_ptr(), out_x.data_ptr(), N,
                                 4 if B == 1 else 0, st), "deslice")
-        fx1, z, out = _empty(dev, N, 128), _empty(dev, N, 256), _empty(dev, N, 128)
+        if not keep:
+            del w
+        fx1, z = (_empty(dev, N, 128), _empty(dev, N, 256)) if keep else (None, None)
+        out = _empty(dev, N, 128)
         # to_out + residual, ln_2, linear_pre, GELU, linear_post + residual: nothing crosses rows - ONE launch (csrc/transmlp.hip)
         if not (self._trans_fuse and (N >= self._trans_fuse_min or self._trans_fuse_fwd_small) and ops.trans_mlp_fwd(
                 out_x, fx_in, P[f"{a}.to_out.0.weight"], P[f"{a}.to_out.0.bias"], P[f"{prefix}.ln_2.weight"], P[f"{prefix}.ln_2.bias"],
                 P[f"{prefix}.mlp.linear_pre.0.weight"], P[f"{prefix}.mlp.linear_pre.0.bias"], P[f"{prefix}.mlp.linear_post.weight"],
                 P[f"{prefix}.mlp.linear_post.bias"], fx1, z, out)):
+            if not keep:   # (the three single-layer launches pass fx1 and z through memory: temporaries of this call)
+                fx1, z = _empty(dev, N, 128), _empty(dev, N, 256)
             ops.rowtile_chain(N, [Seg(out_x)], [LayerSpec(P[f"{a}.to_out.0.weight"], P[f"{a}.to_out.0.bias"])], [fx1],
                               res=[fx_in])
             ops.rowtile_chain(N, [Seg(fx1)],
@@ -941,6 +996,8 @@ class Engine:
             ops.rowtile_chain(N, [Seg(z, width=128, ld=256), Seg(z, width=128, ld=256, offset=128)],
                               [LayerSpec(P[f"{prefix}.mlp.linear_post.weight"], P[f"{prefix}.mlp.linear_post.bias"])], [out],
                               in_op=L.IN_GELU, res=[fx1])
+        if not keep:
+            return out, None
         sv = dict(prefix=prefix, fx_in=fx_in, fx_mid=fx_mid, x_mid=x_mid, w=w, token=token, norm=norm, attn=attn,
                   out_token=out_token, out_x=out_x, fx1=fx1, z=z)
         return out, sv
@@ -1118,7 +1175,7 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # finite-volume integrator (FVscheme.py:618-724 -> conserved_form :50-274)
     # ------------------------------------------------------------------------------------------------------------
-    def fvm_fwd(self, dec, uv_old, pl, want_outputs=True, train_loss=None):
+    def fvm_fwd(self, dec, uv_old, pl, want_outputs=True, train_loss=None, keep=True):
         lib = L.load()
         st = L.stream_ptr()
         N, E, C, B = pl.N, pl.E, pl.C, pl.B
@@ -1126,8 +1183,9 @@ class Engine:
         phi = _empty(dev, N, 8)
         L.check(lib.gfv_phi_fwd(dec.data_ptr(), pl.y.data_ptr(), pl.node_type.data_ptr(), uv_old.data_ptr(), phi.data_ptr(),
                                 N, self.mode, st), "phi_fwd")
-        losses, uvp_node, uvp_cell, sv = self.fvm_core_fwd(phi, pl, want_outputs, train_loss=train_loss)
-        sv["dec"] = dec
+        losses, uvp_node, uvp_cell, sv = self.fvm_core_fwd(phi, pl, want_outputs, train_loss=train_loss, keep=keep)
+        if keep:
+            sv["dec"] = dec
         return losses, uvp_node, uvp_cell, sv
 
     def _fvm_mesh(self, pl, raw=False):
@@ -1153,13 +1211,15 @@ class Engine:
             self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)   # (arrival counter of the tail launch: zero between launches)
         return self._fvm_cnt
 
-    def fvm_core_fwd(self, phi, pl, want_outputs=True, raw_outputs=False, train_loss=None):
+    def fvm_core_fwd(self, phi, pl, want_outputs=True, raw_outputs=False, train_loss=None, keep=True):
         """phi [N,8] = (uvp_new, uv_hat, uv_old, 0) -> residual losses [B,4], smoothed node field, cell field.
         train_loss = (hyper [8], loss [1], gloss [B,4]) device tensors: the training loss of pre_train_Adam.py:177-184 and its
         gradient with respect to the four residuals are formed behind the residual norms (TrainStep).
         raw_outputs: the two fields as the reference's stand-alone Intergrator returns them (FVscheme.py:253-262,718-724) - the
         smoothed node field before the Dirichlet overwrite and neither field re-dimensionalised (importer.py:223-231 does both
-        afterwards)."""
+        afterwards).
+        keep=False: forward only - grad, Ff, phic and cres are temporaries of this call (each is read by a later launch of it),
+        the squared residual norms `sums` are not written, None comes back for the saved state."""
         lib = L.load()
         st = L.stream_ptr()
         N, E, C, B = pl.N, pl.E, pl.C, pl.B
@@ -1183,14 +1243,16 @@ class Engine:
                                     pl.dt.data_ptr(), pl.uvp_dim.data_ptr(), pl.sigma.data_ptr(), phic.data_ptr(),
                                     cres.data_ptr(), None if uvp_cell is None else uvp_cell.data_ptr(), C, self.nc,
                                     None if gradc is None else gradc.data_ptr(), st), "cell_fwd")
-        sums, losses = _empty(dev, B, 4), _empty(dev, B, 4)
+        sums, losses = (_empty(dev, B, 4) if (keep or not self._fvm_fuse) else None), _empty(dev, B, 4)
         uvp_node = _empty(dev, N, 3) if want_outputs else None
+        if not keep:
+            del Ff, grad, gradc
         if self._fvm_fuse:
             # residual norms + (train: the training loss and its gradient, by the workgroup that sees the last graph's norms) +
             # node smoothing as ONE launch (round 6, csrc/fvm.hip fvm_tail_kernel)
             tl = train_loss
             L.check(lib.gfv_fvm_fwd_tail(self._fvm_mesh(pl, raw_outputs), cres.data_ptr(), phic.data_ptr(), phi.data_ptr(),
-                                         sums.data_ptr(), losses.data_ptr(), None if uvp_node is None else uvp_node.data_ptr(),
+                                         L.ptr(sums), losses.data_ptr(), None if uvp_node is None else uvp_node.data_ptr(),
                                          None if tl is None else tl[0].data_ptr(), None if tl is None else tl[1].data_ptr(),
                                          None if tl is None else tl[2].data_ptr(), self._fvm_counter(dev).data_ptr(), st), "fvm_fwd_tail")
         else:
@@ -1206,6 +1268,8 @@ class Engine:
                                                train_loss[2].data_ptr(), st), "train_loss")
         if want_outputs and raw_outputs:
             uvp_cell = phic[:, 0:3].clone()
+        if not keep:
+            return losses, uvp_node, uvp_cell, None
         sv = dict(Ff=Ff, cres=cres, sums=sums, phi=phi, grad=grad, phic=phic, gradc=gradc)
         return losses, uvp_node, uvp_cell, sv
 
@@ -1357,15 +1421,17 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # simulator (TransFVGN_v2.py:54-105 / EPD.py:222-270)
     # ------------------------------------------------------------------------------------------------------------
-    def simulator_fwd(self, P, x, ea16, pl, prefix="simulator"):
+    def simulator_fwd(self, P, x, ea16, pl, prefix="simulator", keep=True):
+        """keep=False: forward only - no MLP saves anything, every intermediate goes back to the allocator when its last consumer
+        has been launched (all of them on the calling stream), None comes back for the saved state."""
         N, E = pl.N, pl.E
-        xn, _, sv_nenc = self.mlp3_fwd(P, f"{prefix}.encoder.nb_encoder", N, [Seg(x, width=12, ld=12)])
-        en, _, sv_eenc = self.mlp3_fwd(P, f"{prefix}.encoder.eb_encoder", E, [Seg(ea16, width=15, ld=16)])
+        xn, _, sv_nenc = self.mlp3_fwd(P, f"{prefix}.encoder.nb_encoder", N, [Seg(x, width=12, ld=12)], keep=keep)
+        en, _, sv_eenc = self.mlp3_fwd(P, f"{prefix}.encoder.eb_encoder", E, [Seg(ea16, width=15, ld=16)], keep=keep)
         procs = []
         if self.net == "EPD":
             blocks = []
             for ig in range(self.mp):
-                xn, en, sv = self.gn_fwd(P, f"{prefix}.GN_block_list.{ig}", xn, en, pl)
+                xn, en, sv = self.gn_fwd(P, f"{prefix}.GN_block_list.{ig}", xn, en, pl, keep=keep)
                 blocks.append(sv)
             procs.append(dict(blocks=blocks, trans=None))
         else:
@@ -1376,11 +1442,13 @@ class Engine:
                 emb = xn
                 blocks = []
                 for ig in range(self.mp):
-                    xn, en, sv = self.gn_fwd(P, f"{pp}.GN_block_list.{ig}", xn, en, pl)
+                    xn, en, sv = self.gn_fwd(P, f"{pp}.GN_block_list.{ig}", xn, en, pl, keep=keep)
                     blocks.append(sv)
-                xn, svt = self.trans_fwd(P, f"{pp}.TransBlock", xn, emb, pl)
+                xn, svt = self.trans_fwd(P, f"{pp}.TransBlock", xn, emb, pl, keep=keep)
                 procs.append(dict(blocks=blocks, trans=svt))
-        dec, _, sv_dec = self.mlp3_fwd(P, f"{prefix}.decoder.node_decode_module", N, [Seg(xn)], ln=False)
+        dec, _, sv_dec = self.mlp3_fwd(P, f"{prefix}.decoder.node_decode_module", N, [Seg(xn)], ln=False, keep=keep)
+        if not keep:
+            return dec, None
         return dec, dict(sv_nenc=sv_nenc, sv_eenc=sv_eenc, procs=procs, sv_dec=sv_dec)
 
     def simulator_bwd(self, P, sv, g_dec, grads, pl):
@@ -1425,23 +1493,37 @@ class Engine:
     # whole model (importer.py:156-240)
     # ------------------------------------------------------------------------------------------------------------
     def forward(self, P, buffers, x, pl, *, norm_global=True, accumulate=True, want_outputs=True, want_edge_attr15=True,
-                before_prep=None, x_raw=None, train_loss=None):
-        """before_prep: main-stream work of the caller that only the input preparation waits for (TrainStep's restore of the
+                before_prep=None, x_raw=None, train_loss=None, keep=True, static_weights=False):
+        """keep=False: the forward-only step (gfv/rollout.py, NNmodel.forward under torch.no_grad()) - the same launches on the same
+        kernel families with the same arguments except the save pointers, which are NULL wherever no later launch of this forward
+        reads the tensor; the outputs have the bits of the saving forward's, None comes back for the saved state.
+        static_weights: the caller built the forward weight images for these parameter VALUES (`build_static_images`) and
+        vouches that they have not changed: no maximum, no image build in this call, the images stay valid after it.
+        before_prep: main-stream work of the caller that only the input preparation waits for (TrainStep's restore of the
         un-normalised node state): issued BEHIND the fork, so that the side stream's image build - which the first encoder launch
         waits for, ~16 us in round 5's timelines - starts a copy and a cross-queue signal earlier."""
-        # the per-step weight images are built on the side stream while the input preparation runs on the main one
-        with self.fork():
-            prev = self._wi_enter("fwd", P)
+        if static_weights:
+            prev = self._wi_static_enter(P)
+        else:
+            # the per-step weight images are built on the side stream while the input preparation runs on the main one
+            with self.fork():
+                prev = self._wi_enter("fwd", P)
         try:
             if before_prep is not None:
                 before_prep()
             uv_old, ea16, ea15 = self.prep_fwd(x, buffers, pl, norm_global, accumulate, want_edge_attr15, x_raw=x_raw)
-            self.join()
-            dec, sv_sim = self.simulator_fwd(P, x, ea16, pl)
+            if not static_weights:
+                self.join()
+            dec, sv_sim = self.simulator_fwd(P, x, ea16, pl, keep=keep)
         finally:
-            self._wi_exit("fwd", prev)
-        losses, uvp_node, uvp_cell, sv_fvm = self.fvm_fwd(dec, uv_old, pl, want_outputs, train_loss=train_loss)
-        return losses, uvp_node, uvp_cell, ea15, dict(sim=sv_sim, fvm=sv_fvm)
+            if not static_weights:
+                self._wi_exit("fwd", prev)
+            elif self.f16split:
+                ops.set_weight_images(prev)
+        if not keep:
+            del ea16
+        losses, uvp_node, uvp_cell, sv_fvm = self.fvm_fwd(dec, uv_old, pl, want_outputs, train_loss=train_loss, keep=keep)
+        return losses, uvp_node, uvp_cell, ea15, (dict(sim=sv_sim, fvm=sv_fvm) if keep else None)
 
     def backward(self, P, ctx, gloss, grads, pl):
         """gloss [B,4] = dL/d(cont, mom_x, mom_y, press); fills `grads` (name -> preallocated tensor)."""

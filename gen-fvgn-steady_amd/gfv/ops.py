@@ -365,7 +365,7 @@ def trans_mlp_fwd(x, res, Wout, bout, gamma, beta, Wpre, bpre, Wpost, bpost, fx1
     a.x, a.res, a.img_out, a.img_pre, a.img_post = x.data_ptr(), res.data_ptr(), hs[0], hs[1], hs[2]
     a.b_out, a.b_pre, a.b_post = _p(bout), _p(bpre), _p(bpost)
     a.gamma, a.beta, a.wmax = gamma.data_ptr(), beta.data_ptr(), _WI.wmax.data_ptr()
-    a.fx1, a.z, a.out, a.M = fx1.data_ptr(), z.data_ptr(), out.data_ptr(), x.shape[0]
+    a.fx1, a.z, a.out, a.M = _p(fx1), _p(z), out.data_ptr(), x.shape[0]   # (fx1 = z = None: the forward-only form)
     L.check(lib.gfv_trans_mlp_fwd(C.byref(a), L.stream_ptr()), "gfv_trans_mlp_fwd")
     return True
 

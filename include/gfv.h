@@ -431,6 +431,7 @@ int gfv_slice_softmax_bwd(const float* xmid, const float* Ws, const float* bs, c
 /* partial[chunk][h*32+g][0:16] = sum_n w[n,h,g] a[n,h,:], [16] = sum_n w[n,h,g] */
 int gfv_slice_token_partial(const float* w, const float* a, const int32_t* chunk_beg, const int32_t* chunk_end,
                             int32_t n_chunks, float* partial, void* stream);
+/* (token, norm, attn: what the backward reads - each may be NULL in a forward-only step) */
 int gfv_slice_attention_fwd(const float* partial, const int32_t* gchunk_ptr, int32_t B, const float* Wq, const float* Wk,
                             const float* Wv, float* token, float* norm, float* attn, float* out_token, void* stream);
 /* dW_partial [B*8][3][16][16] (q,k,v), reduce with gfv_reduce_partials */
@@ -606,7 +607,8 @@ typedef struct {
   const int32_t* xo_rowptr; const int32_t* xo_in; const float* xo_B; const float* sumB;   /* stencil in sender order */
 } gfv_fvm_mesh_t;
 /* forward tail: gfv_graph_loss + gfv_train_loss_dev (hyper != NULL; its last-arriving workgroup) + gfv_cell_to_node (uvp_node !=
- * NULL) as ONE launch.  counter: one int32 of the caller's, zero before the first launch (the launch leaves it zero). */
+ * NULL) as ONE launch.  counter: one int32 of the caller's, zero before the first launch (the launch leaves it zero).
+ * sums [B,4] (the squared residual norms the backward reads) may be NULL in a forward-only step. */
 int gfv_fvm_fwd_tail(const gfv_fvm_mesh_t* mesh, const float* cres, const float* phic, const float* phi, float* sums, float* losses,
                      float* uvp_node, const float* hyper, float* loss, float* gloss, int32_t* counter, void* stream);
 /* backward of the conserved form from the loss gradients to the gradient of the decoder output, THREE launches (was six:
@@ -735,7 +737,7 @@ typedef struct {
   const float* beta;
   const float* wmax;
   float* fx1;            /* [M,128] out (saved for the backward) */
-  float* z;              /* [M,256] out (saved) */
+  float* z;              /* [M,256] out (saved); fx1 == z == NULL: the forward-only form - neither is stored, `out` has the same bits */
   float* out;            /* [M,128] */
   int32_t M, reserved;
 } gfv_trans_mlp_t;
@@ -785,6 +787,22 @@ int gfv_stream_wait(void* waiter_stream, void* waited_stream);
  * to it.  A later position only adds ordering (the run's leading wait then covers more of the main stream).  For steps whose main
  * stream runs dry while the host issues a side-stream burst (small meshes).  Returns the number of runs moved, or GFV_ERR_ARG. */
 int gfv_record_delay_side(int64_t handle, void* main_stream, int32_t k);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Forward-only rollout (gfv/rollout.py; solve_without_grad_GPU.py:117-173).  The end of a rollout step as ONE launch:
+ *   x_backup[:, 0:3] = uvp_node;  x = x_backup          (x_backup, x [N,12], 16-byte aligned)
+ *   history[k, b, 0:4] = losses[b];  history[k, b, 4] = || uvp_node - uvp_prev ||_2;  history[k, b, 5] = || uvp_node ||_2
+ * over the nodes of graph b, uvp_prev being what x_backup[:, 0:3] held.  k = state[0]; the launch itself stores k + 1 there, so
+ * one recorded launch replays for step after step.  state: two int32 of the caller's (step counter, arrival counter), the second
+ * zero before the first launch (the launch leaves it zero).  history [K_max, B, 6]; with k >= K_max nothing is written to it and
+ * k stays.  chunk_beg / chunk_end [n_chunks]: node ranges that never cross a graph, gchunk_ptr [B + 1] the chunk range of each
+ * graph (the plan's slice chunks); partial_ws: 2 * n_chunks doubles.  Sums in a fixed order (double partial sums per chunk, folded
+ * per graph by the workgroup that arrives last): no floating-point atomics, results identical run to run.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer or a size < 1.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gfv_rollout_advance(const float* uvp_node, float* x_backup, float* x, int32_t N, const int32_t* chunk_beg,
+                        const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* losses,
+                        double* partial_ws, float* history, int32_t K_max, int32_t* state, void* stream);
 
 #ifdef __cplusplus
 }
