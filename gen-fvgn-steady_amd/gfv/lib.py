@@ -97,9 +97,28 @@ class FvmMesh(C.Structure):
                     "xo_rowptr", "xo_in", "xo_B", "sumB")])
 
 
+POOL_MAX_GRAPHS, POOL_MAX_ATTRS, POOL_ROW_HEAD = 64, 56, 8   # GFV_POOL_* of include/gfv.h
+POOL_COPY, POOL_ADD, POOL_ROWPTR, POOL_FILL = 0, 1, 2, 3
+
+
+class PoolArgs(C.Structure):
+    """gfv_pool_args_t (include/gfv.h): the arena and the batch of one gfv_pool_assemble launch."""
+    _fields_ = [("table_host", C.c_void_p), ("table_dev", C.c_void_p), ("n_entries", C.c_int32), ("n_attrs", C.c_int32),
+                ("max_graphs", C.c_int32), ("slice_chunk", C.c_int32), ("max_chunks", C.c_int64),
+                ("attr_info", C.c_int32 * POOL_MAX_ATTRS), ("dst", C.c_void_p * POOL_MAX_ATTRS),
+                ("dst_cap_words", C.c_int64 * POOL_MAX_ATTRS), ("small", C.c_void_p * 6), ("B", C.c_int32),
+                ("reserved", C.c_int32), ("idx", C.c_int32 * POOL_MAX_GRAPHS)]
+
+
 _lib = None
 
 _SIGNATURES = {
+    "gfv_pool_args_bytes": (C.c_size_t, []),
+    "gfv_pool_table_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gfv_pool_table_check": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gfv_pool_assemble": (C.c_int, [C.POINTER(PoolArgs), C.c_void_p]),
+    "gfv_pool_payback": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                   C.c_int64, C.c_void_p, C.c_void_p]),
     "gfv_abi_version": (C.c_int, []),
     "gfv_struct_size": (C.c_int, [C.c_int32]),
     "gfv_seg_gather_sum": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -278,6 +297,9 @@ def load(raw=False):
         if lib.gfv_struct_size(which) != C.sizeof(st):
             raise RuntimeError(f"libgfv.so: struct {st.__name__} is {lib.gfv_struct_size(which)} bytes in the library, "
                                f"{C.sizeof(st)} in the binding")
+    if lib.gfv_pool_args_bytes() != C.sizeof(PoolArgs):
+        raise RuntimeError(f"libgfv.so: gfv_pool_args_t is {lib.gfv_pool_args_bytes()} bytes in the library, "
+                           f"{C.sizeof(PoolArgs)} in the binding")
     _lib = lib
     return lib if (_recording is None or raw) else _recording
 

@@ -8,6 +8,10 @@ on the device by ONE launch of ``gfv_concat_offsets`` - a batch is block diagona
 concatenation of the per-mesh tensors with the node / face / cell / incidence offset of the mesh added to its indices
 (the ``__inc__`` rules of ``CustomGraphData``) - and predictions are written back in place.  The assembled plan is
 tensor-for-tensor equal to ``build_plan(build_batch(meshes))`` (tests/test_pool_gpu.py).
+
+For training over the pool with a new batch every step there is ``DevicePool.arena`` -> ``BatchArena``: the same batch, assembled
+into FIXED memory by one launch of ``gfv_pool_assemble`` with no per-step allocation or host-built table (what
+``gfv.pool_trainer.PoolTrainStep`` replays recorded steps over), and ``DevicePool.add_variant``: entries that share a topology.
 """
 from __future__ import annotations
 
@@ -31,6 +35,222 @@ _FLOAT_ATTRS = ("inv_deg", "y", "pos", "x_B", "xo_B", "sumB", "rn", "An", "fpos"
 _FILL = dict(batch="n", cbatch="c")   # graph id per node / cell
 
 _DESC = np.dtype([("src", "<u8"), ("dst", "<u8"), ("n", "<i8"), ("kind", "<i4"), ("add", "<i4")])
+
+_VARIANT_OWNED = ("y", "theta", "dt", "uvp_dim")      # (+ x and the bc record): what reset_env writes
+_SIZE_KEYS = ("n", "e", "c", "k", "s", "nchunk")      # the head columns of the source table (include/gfv.h gfv_pool_args_t)
+_KIND_ID = {"-": 0, "n": 1, "e": 2, "e2": 3, "c": 4, "k": 5, "s": 6}
+# rows of every copied attribute in units of a size ("g": one row per graph); checked against every entry when an arena is built
+_ROWS_OF = dict(es="e", er="e", n_col_node="e2", x_out="s", xo_in="s", knode="k", s_col="e", r_col="e", kface="k", n_col_edge2="e2",
+                kcell="k", ncell="k", fk="k", node_type="n", ftype="e", inv_deg="n", y="n", pos="n", x_B="s", xo_B="s", sumB="n",
+                rn="n", An="n", fpos="e", kS="k", centroid="c", area="c", theta="g", sigma="g", uvp_dim="g", dt="g", x="n", x_raw="n")
+
+
+def entry_signature(size):
+    """(nodes, faces, cells, incidences, stencil entries, slice chunks) of one pool entry."""
+    return tuple(int(size[k]) for k in _SIZE_KEYS)
+
+
+def batch_signature(sizes, indices):
+    """The ordered size signature of a batch: two batches with the same signature are assembled into the same memory with the
+    same shapes, so the launches of a step over one are the launches of a step over the other."""
+    return tuple(entry_signature(sizes[int(i)]) for i in indices)
+
+
+def batch_totals(sizes, indices):
+    return {k: sum(int(sizes[int(i)][k]) for i in indices) for k in _SIZE_KEYS}
+
+
+def default_capacity(sizes, max_graphs):
+    """Totals no batch of up to `max_graphs` entries exceeds: per size, the sum of its `max_graphs` largest values."""
+    if int(max_graphs) < 1:
+        raise ValueError("max_graphs must be at least 1")
+    return {k: sum(sorted((int(s[k]) for s in sizes), reverse=True)[:int(max_graphs)]) for k in _SIZE_KEYS}
+
+
+def check_fits(totals, B, capacity, max_graphs):
+    """ValueError when a batch of B entries with these totals does not fit an arena of this capacity."""
+    if B < 1:
+        raise ValueError("a batch needs at least one entry")
+    if B > max_graphs:
+        raise ValueError(f"a batch of {B} entries exceeds the arena's capacity of {max_graphs} graphs")
+    for k in _SIZE_KEYS:
+        if totals[k] > capacity[k]:
+            raise ValueError(f"the batch needs {totals[k]} of '{k}', the arena holds {capacity[k]}: build it with larger max_sizes")
+
+
+def _rows(size, kind, B=1):
+    return B if kind == "g" else (2 * size["e"] if kind == "e2" else size[kind])
+
+
+class BatchArena:
+    """Fixed memory every batch of a DevicePool is assembled into (include/gfv.h gfv_pool_assemble: ONE launch, the entry indices
+    by value, offsets formed on the device).  `load(indices)` returns views of that memory: for batches of equal size signature
+    every tensor has the same `data_ptr()` and shape as last time - a recorded launch list of a step over one such batch is valid
+    for every other (gfv/pool_trainer.py).  A later load overwrites what an earlier one returned."""
+
+    VIEW_CACHE = 256
+
+    def __init__(self, pool, max_graphs, max_sizes=None):
+        self.pool = pool
+        self.max_graphs = int(max_graphs)
+        if not 1 <= self.max_graphs <= L.POOL_MAX_GRAPHS:
+            raise ValueError(f"max_graphs must be in [1, {L.POOL_MAX_GRAPHS}]")
+        cap = default_capacity(pool.sizes, self.max_graphs) if max_sizes is None else {k: int(max_sizes[k]) for k in _SIZE_KEYS}
+        self.capacity = cap
+        dev = pool.device
+        B = self.max_graphs
+        # attributes of the launch, in table order: (name, mode, offset kind, rows kind, words per row, dtype)
+        attrs = []
+        for a, k in _INT_ATTRS.items():
+            attrs.append((a, L.POOL_COPY if k == "-" else L.POOL_ADD, k))
+        for a, (_, nnz) in _ROWPTRS.items():
+            attrs.append((a, L.POOL_ROWPTR, nnz))
+        for a in _FLOAT_ATTRS + ("x", "x_raw"):
+            attrs.append((a, L.POOL_COPY, "-"))
+        for a, k in _FILL.items():
+            attrs.append((a, L.POOL_FILL, "-"))
+        self.attrs = attrs
+        self.names = [a[0] for a in attrs]
+        A = len(attrs)
+        assert A <= L.POOL_MAX_ATTRS
+        self._buf, self._row_shape = {}, {}
+        args = L.PoolArgs()
+        for j, (a, mode, k) in enumerate(attrs):
+            if mode == L.POOL_FILL:
+                rows, row_shape, dtype = cap[_FILL[a]], (), torch.int32
+            elif mode == L.POOL_ROWPTR:
+                rows, row_shape, dtype = cap[_ROWPTRS[a][0]] + 1, (), torch.int32
+            else:
+                _, _, row_shape, dtype = pool._src["x" if a == "x_raw" else a]
+                rows = _rows(cap, _ROWS_OF[a], B)
+            roww = int(np.prod(row_shape)) if row_shape else 1
+            words = rows * roww
+            buf = torch.zeros(max(words, 4), dtype=dtype, device=dev)
+            assert buf.data_ptr() % 16 == 0
+            self._buf[a], self._row_shape[a] = buf, tuple(row_shape)
+            args.attr_info[j] = mode | (_KIND_ID[k] << 4)
+            args.dst[j] = buf.data_ptr()
+            args.dst_cap_words[j] = words
+        small = dict(gnode_ptr=B + 1, gcell_ptr=B + 1, gchunk_ptr=B + 1, gunit_ptr=B + 1, chunk_beg=cap["nchunk"], chunk_end=cap["nchunk"])
+        for j, (a, words) in enumerate(small.items()):
+            self._buf[a] = torch.zeros(max(words, 1), dtype=torch.int32, device=dev)
+            args.small[j] = self._buf[a].data_ptr()
+        args.n_attrs, args.max_graphs, args.slice_chunk, args.max_chunks = A, B, SLICE_CHUNK, cap["nchunk"]
+        self._args = args
+        self.x_attr = self.names.index("x")
+        self._views = {}
+        self._n_tab = -1
+        self._last = None
+        self._build_table()
+
+    # the source table: one row per entry, on the host (argument checks, grid sizes) and on the device (the kernels) -----------------
+    def _build_table(self):
+        pool, A = self.pool, len(self.attrs)
+        tab = np.zeros((pool.n, L.POOL_ROW_HEAD + 2 * A), dtype=np.int64)
+        for c, k in enumerate(_SIZE_KEYS):
+            tab[:, c] = [s[k] for s in pool.sizes]
+        for j, (a, mode, k) in enumerate(self.attrs):
+            if mode == L.POOL_FILL:
+                tab[:, L.POOL_ROW_HEAD + A + j] = [s[_FILL[a]] for s in pool.sizes]
+                continue
+            ptrs, words, row_shape, _ = pool._src["x" if a == "x_raw" else a]
+            tab[:, L.POOL_ROW_HEAD + j] = ptrs.astype(np.int64)
+            tab[:, L.POOL_ROW_HEAD + A + j] = words
+            roww = int(np.prod(row_shape)) if row_shape else 1
+            want = [(_rows(s, _ROWPTRS[a][0]) + 1) if mode == L.POOL_ROWPTR else _rows(s, _ROWS_OF[a]) * roww for s in pool.sizes]
+            if list(words) != want:
+                raise ValueError(f"pool attribute '{a}' does not have the rows its size kind says")
+        self._tab = np.ascontiguousarray(tab)
+        info = (C.c_int32 * A)(*[self._args.attr_info[j] for j in range(A)])
+        rc = L.load(raw=True).gfv_pool_table_check(self._tab.ctypes.data, pool.n, A, C.addressof(info))
+        if rc != 0:
+            raise ValueError("the pool's source table is not valid (gfv_pool_table_check)")
+        self._tab_dev = torch.from_numpy(self._tab).to(pool.device)
+        self._args.table_host, self._args.table_dev = self._tab.ctypes.data, self._tab_dev.data_ptr()
+        self._args.n_entries = pool.n
+        self._entry_sig = [entry_signature(s) for s in pool.sizes]
+        self._n_tab = pool.n
+
+    def signature(self, indices):
+        return batch_signature(self.pool.sizes, indices)
+
+    def _make_views(self, idx):
+        pool, B = self.pool, len(idx)
+        tot = batch_totals(pool.sizes, idx)
+        check_fits(tot, B, self.capacity, self.max_graphs)
+        p = MeshPlan()
+        out = {}
+        for a, mode, k in self.attrs:
+            if mode == L.POOL_FILL:
+                words = tot[_FILL[a]]
+            elif mode == L.POOL_ROWPTR:
+                words = tot[_ROWPTRS[a][0]] + 1
+            else:
+                rs = self._row_shape[a]
+                words = _rows(tot, _ROWS_OF[a], B) * (int(np.prod(rs)) if rs else 1)
+            t = self._buf[a][:words]
+            rs = self._row_shape[a]
+            out[a] = t.view((-1,) + rs) if rs else t
+            if a not in ("x", "x_raw"):
+                setattr(p, a, out[a])
+        for a, words in (("gnode_ptr", B + 1), ("gcell_ptr", B + 1), ("gchunk_ptr", B + 1), ("gunit_ptr", B + 1),
+                         ("chunk_beg", tot["nchunk"]), ("chunk_end", tot["nchunk"])):
+            setattr(p, a, self._buf[a][:words])
+        p.N, p.E, p.C, p.B = tot["n"], tot["e"], tot["c"], B
+        p.S, p.Sg, p.n_chunks, p.device = tot["s"], tot["k"], tot["nchunk"], pool.device
+        p.M = pool.plans[idx[0]].M
+        graph_node = Data(x=out["x"], batch=p.batch, pos=p.pos, num_graphs=B, norm_uvp=True, norm_global=True)
+        graph_node._gfv_pool_plan = p
+        graph_node._gfv_x_raw = out["x_raw"]       # the un-normalised rows (what TrainStep clones into its backup, kept by the arena)
+        graphs = (graph_node, Data(num_graphs=B), Data(num_graphs=B), Data(num_graphs=B),
+                  Data(theta_PDE=p.theta, sigma=p.sigma, uvp_dim=p.uvp_dim, dt_graph=p.dt.view(-1, 1), num_graphs=B))
+        return graphs, p
+
+    def load(self, indices):
+        """-> (graphs, plan) of the batch `indices`, assembled into the arena by one launch on the current stream."""
+        idx = [int(i) for i in indices]
+        pool = self.pool
+        if pool.n != self._n_tab:
+            self._build_table()                    # (entries were added: add_variant)
+        for i in idx:
+            if not 0 <= i < pool.n:
+                raise ValueError(f"pool entry {i} does not exist (the pool holds {pool.n})")
+        sig = tuple(self._entry_sig[i] for i in idx)
+        hit = self._views.get(sig)
+        if hit is None:
+            hit = self._make_views(idx)            # (raises ValueError for a batch beyond the capacity)
+            if len(self._views) >= BatchArena.VIEW_CACHE:
+                self._views.pop(next(iter(self._views)))
+            self._views[sig] = hit
+        args = self._args
+        args.B = len(idx)
+        for b, i in enumerate(idx):
+            args.idx[b] = i
+        rc = L.load().gfv_pool_assemble(C.byref(args), L.stream_ptr())
+        if rc == -1:
+            raise ValueError("gfv_pool_assemble refused the batch (it does not fit the arena, or an index is outside the pool)")
+        L.check(rc, "gfv_pool_assemble")
+        self._last = (idx, sig)
+        return hit
+
+    def x_raw(self, graphs):
+        return graphs[0]._gfv_x_raw
+
+    def payback(self, indices, uvp_node, advance=False):
+        """Write the batch's predicted (u, v, p) [N, 3] back into the pool entries' own `x` (DevicePool.payback as ONE launch; an
+        entry that appears twice takes its later occurrence); advance: also into the arena's un-normalised state, which the next
+        inner step over the same batch then starts from (TrainStep.advance_time)."""
+        idx = [int(i) for i in indices]
+        if self.pool.n != self._n_tab:
+            self._build_table()
+        assert uvp_node.dtype == torch.float32 and uvp_node.is_contiguous() and uvp_node.shape[1] == 3
+        ia = (C.c_int32 * len(idx))(*idx)
+        raw = self._buf["x_raw"].data_ptr() if advance else None
+        rc = L.load().gfv_pool_payback(self._tab.ctypes.data, self._tab_dev.data_ptr(), self.pool.n, len(self.attrs), self.x_attr,
+                                       C.addressof(ia), len(idx), uvp_node.data_ptr(), int(uvp_node.shape[0]), raw, L.stream_ptr())
+        if rc == -1:
+            raise ValueError("gfv_pool_payback refused the batch (index outside the pool, or uvp_node is not the batch's node field)")
+        L.check(rc, "gfv_pool_payback")
 
 
 class DevicePool:
@@ -180,6 +400,43 @@ class DevicePool:
         x[:, 3:12] = p.theta
         p.y[:, 0] = u / np.float32(U)
         p.y[:, 1] = 0.0
+
+    # ------------------------------------------------------------------------------------------------------------
+    def add_variant(self, i, fields=None, **sampled):
+        """A new entry over the topology of entry `i` -> its index.  The reference fills its pool by walking the same few mesh
+        files again and again with freshly drawn PDE coefficients (Graph_loader.py:98-114: `transform_mesh` of a mesh that is
+        already loaded); here such an entry SHARES every structural tensor of entry `i` (same storage, no copy) and owns only what
+        `reset_env` changes: the node state `x`, the Dirichlet targets `y`, `theta`, `dt`, `uvp_dim` and the `bc` record.
+        `sampled`: as for `reset_env` (applied to the new entry, which restarts its field); `fields` [N, 3]: the (u, v, p) state
+        the entry starts from instead."""
+        i = int(i)
+        src = self.plans[i]
+        p = MeshPlan()
+        p.__dict__.update({k: v for k, v in vars(src).items() if not k.startswith("_")})
+        for a in _VARIANT_OWNED:
+            setattr(p, a, getattr(src, a).clone())
+        v = self.n
+        self.plans.append(p)
+        self.x.append(self.x[i].clone())
+        self.sizes.append(dict(self.sizes[i]))
+        self.bc.append(None if self.bc[i] is None else dict(self.bc[i]))
+        self.pos64.append(self.pos64[i])
+        for a, (ptrs, words, row_shape, dtype) in self._src.items():
+            t = self.x[v] if a == "x" else getattr(p, a)
+            self._src[a] = (np.append(ptrs, np.uint64(t.data_ptr())), np.append(words, np.int64(t.numel())), row_shape, dtype)
+        self.n = v + 1
+        if sampled:
+            self.reset_env(v, **sampled)
+        if fields is not None:
+            f = torch.as_tensor(fields, dtype=torch.float32).to(self.device)
+            self.x[v][:, 0:3].copy_(f.reshape(-1, 3))
+        return v
+
+    def arena(self, max_graphs, max_sizes=None):
+        """Fixed-capacity device memory for batches of up to `max_graphs` entries -> BatchArena.  max_sizes: totals of a batch
+        (keys n, e, c, k, s, nchunk: nodes, faces, cells, incidences, stencil entries, slice chunks); default: the `max_graphs`
+        largest entries of the pool, size by size."""
+        return BatchArena(self, max_graphs, max_sizes)
 
     # ------------------------------------------------------------------------------------------------------------
     def payback(self, indices, uvp_node):

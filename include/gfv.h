@@ -804,6 +804,63 @@ int gfv_rollout_advance(const float* uvp_node, float* x_backup, float* x, int32_
                         const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* losses,
                         double* partial_ws, float* history, int32_t K_max, int32_t* state, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Pool training (gfv/pool.py BatchArena, gfv/pool_trainer.py; the changing-batch loop of pre_train_Adam.py:112-198 with
+ * Data_Pool.payback, Graph_loader.py:370-396): a batch of ANY entries of the device-resident pool assembled into FIXED memory
+ * by one launch, and the prediction written back by one launch.
+ *
+ * The source table, built once per pool: one row of GFV_POOL_ROW_HEAD + 2 * n_attrs int64 per entry -
+ *   [n nodes, n faces, n cells, n incidences, n stencil entries, n slice chunks, 0, 0 | device pointer of every pooled attribute |
+ *    32-bit words of every pooled attribute]
+ * - the same bytes in host memory (argument checks, grid sizes) and in device memory (read by the kernels).  What an attribute is
+ * says attr_info[a] = mode | offset kind << 4:
+ *   mode GFV_POOL_COPY    words copied as they are (floats, type ids)
+ *        GFV_POOL_ADD     int32 indices: the entry's words + the offset of its position in the batch
+ *        GFV_POOL_ROWPTR  a CSR row pointer (rows + 1 words): all but the last word of every entry, the last word too of the
+ *                         last one, + the offset of the non-zero kind
+ *        GFV_POOL_FILL    no source: `words` times the position in the batch (graph id per node / cell)
+ *   offset kind 0 none, 1 nodes, 2 faces, 3 2 x faces, 4 cells, 5 incidences, 6 stencil entries.
+ * The offsets are formed INSIDE the launch by a prefix sum over the B entries, whose indices travel by value in the launch's
+ * argument block: a buffer the host rewrites for the next step would race with a launch that is still queued.  The same launch
+ * writes the small per-graph arrays: gnode_ptr, gcell_ptr, gchunk_ptr, gunit_ptr [B + 1] and chunk_beg / chunk_end (node chunks of
+ * `slice_chunk` rows that never cross a graph), in small[0 .. 5] in that order.  Streaming copies: 16-byte stores always (every
+ * dst[a] is 16-byte aligned), 16-byte loads where the source position allows.
+ * gfv_pool_assemble returns GFV_ERR_ARG - before anything touches a device - for a NULL table or argument, B < 1, B above
+ * max_graphs or GFV_POOL_MAX_GRAPHS, an index outside [0, n_entries), an attribute whose batch exceeds dst_cap_words[a], more
+ * chunks than max_chunks, a misaligned destination.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_POOL_MAX_GRAPHS 64
+#define GFV_POOL_MAX_ATTRS 56
+#define GFV_POOL_ROW_HEAD 8
+enum { GFV_POOL_COPY = 0, GFV_POOL_ADD = 1, GFV_POOL_ROWPTR = 2, GFV_POOL_FILL = 3 };
+typedef struct {
+  const int64_t* table_host; /* [n_entries, GFV_POOL_ROW_HEAD + 2 * n_attrs] */
+  const int64_t* table_dev;  /* the same bytes in device memory */
+  int32_t n_entries, n_attrs;
+  int32_t max_graphs;        /* capacity of the small per-graph arrays: max_graphs + 1 words each */
+  int32_t slice_chunk;       /* nodes per chunk of chunk_beg / chunk_end */
+  int64_t max_chunks;        /* capacity of chunk_beg / chunk_end */
+  int32_t attr_info[GFV_POOL_MAX_ATTRS];
+  void* dst[GFV_POOL_MAX_ATTRS];             /* the batched tensor of every attribute, 16-byte aligned */
+  int64_t dst_cap_words[GFV_POOL_MAX_ATTRS]; /* its capacity */
+  int32_t* small[6];
+  int32_t B, reserved;
+  int32_t idx[GFV_POOL_MAX_GRAPHS];          /* the entries of the batch, in order */
+} gfv_pool_args_t;
+size_t gfv_pool_args_bytes(void);                /* sizeof of the struct above as the library was compiled */
+size_t gfv_pool_table_bytes(int32_t n_entries, int32_t n_attrs);
+/* host-side validation of a table: sizes >= 0 and within int32, every attribute with words > 0 has a 4-byte aligned source unless
+ * it is a fill, a row pointer has at least one word.  GFV_OK or GFV_ERR_ARG; touches no device. */
+int gfv_pool_table_check(const int64_t* table_host, int32_t n_entries, int32_t n_attrs, const int32_t* attr_info);
+int gfv_pool_assemble(const gfv_pool_args_t* args, void* stream);
+/* The inverse of the assembly of the node state: rows of uvp_node [N, 3] of the batch go into columns 0 .. 2 of each entry's own
+ * x [n_i, 12] - the attribute `x_attr` of the table -; raw != NULL: also into columns 0 .. 2 of raw [N, 12], the arena's
+ * un-normalised state the next inner step of the same batch starts from.  An entry that appears more than once in the batch takes
+ * its LAST occurrence; the earlier ones are skipped - one writer per word.  N must equal the batch's node count.
+ * GFV_ERR_ARG as for gfv_pool_assemble, and for a NULL uvp_node, x_attr outside the table or a wrong N. */
+int gfv_pool_payback(const int64_t* table_host, const int64_t* table_dev, int32_t n_entries, int32_t n_attrs, int32_t x_attr,
+                     const int32_t* idx, int32_t B, const float* uvp_node, int64_t N, float* raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
