@@ -245,6 +245,18 @@ _SIGNATURES = {
     "gfv_record_free": (C.c_int, [C.c_int64]),
     "gfv_stream_wait": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gfv_record_delay_side": (C.c_int, [C.c_int64, C.c_void_p, C.c_int32]),
+    "gfv_lbfgs_workspace_doubles": (C.c_size_t, [C.c_int32, C.c_int64]),
+    "gfv_lbfgs_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_double, C.c_int32, C.c_void_p]),
+    "gfv_lbfgs_multidot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_void_p]),
+    "gfv_lbfgs_coef": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32,
+                                 C.c_void_p]),
+    "gfv_lbfgs_combine": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
+    "gfv_lbfgs_dot": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p]),
+    "gfv_lbfgs_axpy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 

@@ -8,6 +8,10 @@ What it does to the model: the parameters become views of one flat buffer (16-by
 layout, which `step()` recognises and feeds to the kernel as it is (otherwise the gradients are gathered into a flat buffer
 first: still one optimiser launch).  Supported: one parameter group, `weight_decay=0`, `amsgrad=False`, `maximize=False`
 (torch.optim.Adam's defaults, what both reference drivers use); anything else raises at construction.
+
+`gfv.optim.LBFGS` - torch.optim.LBFGS for the closure loop of solve_with_grad_GPU_LBFGS.py:67-202, the same way: one import
+changed, the same flat buffer, and the search direction in four launches (csrc/lbfgs.hip) instead of ~4 m launches and 2 m host
+synchronisations of the two-loop recursion over history_size = m vectors.
 """
 from __future__ import annotations
 
@@ -158,3 +162,278 @@ class Adam(torch.optim.Optimizer):
             if k != "params":
                 self.param_groups[0][k] = v
         self._sync_hyper(steps_done=0.0 if step is None else step)
+
+
+class LBFGS(torch.optim.Optimizer):
+    """torch.optim.LBFGS with the same constructor, defaults, `step(closure)` semantics and checkpoint keys, on the library's
+    L-BFGS launches (include/gfv.h gfv_lbfgs_*).
+
+    Per iteration: pair, multidot, coef, combine - the two-loop recursion on coefficients over {s_i, y_i, g} with their dot
+    products kept in double on the device (same gamma = ys / y.y, same skip rule ys > 1e-10) - then ONE read of a 128-byte
+    result block; per closure evaluation: one masked copy + dot launch and ONE read (loss, g.d, max|g|, sum|g|).  Nothing on
+    the host is proportional to history_size or to the number of parameters.  The strong-Wolfe search runs on host scalars
+    (gfv/linesearch.py); the gradients of its live points stay in three device slots, and the point it returns hands its
+    gradient on without another evaluation, as torch does.
+
+    Padding is not data: the flat layout pads every tensor to 16 bytes and the padding of a flat gradient is undefined, so the
+    gradient enters through a masked copy and every vector this object owns is zero there; the parameters' padding is never
+    written.  A parameter whose `.grad` is None contributes zeros (torch's `_gather_flat_grad`).
+
+    Memory: the history is 2 * (history_size + 1) * n * 4 bytes (955 MB for the 1.18 M parameters of the model at
+    history_size = 100; torch's grows to 2 * history_size * n * 4), allocated ONCE at construction - the extra slot holds the
+    candidate pair, so that a rejected one does not cost the oldest.
+
+    Raises at construction: ValueError for more than one parameter group, history_size outside [1, 128] or a
+    `line_search_fn` other than None / "strong_wolfe"; RuntimeError for parameters that are not fp32 on the GPU."""
+
+    MAX_HISTORY = 128
+    # the flat buffer of the parameters and the recognition of NNmodel's flat gradient are Adam's
+    _adopt, _flat_grad, _none_grad_ok = Adam._adopt, Adam._flat_grad, Adam._none_grad_ok
+
+    def __init__(self, params, lr=1, max_iter=20, max_eval=None, tolerance_grad=1e-7, tolerance_change=1e-9, history_size=100,
+                 line_search_fn=None):
+        if not 0.0 <= float(lr):
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if line_search_fn not in (None, "strong_wolfe"):
+            raise ValueError("gfv.optim.LBFGS: line_search_fn is None or 'strong_wolfe'")
+        if not 1 <= int(history_size) <= self.MAX_HISTORY:
+            raise ValueError(f"gfv.optim.LBFGS: history_size in [1, {self.MAX_HISTORY}] (the coefficient launch is one workgroup)")
+        if max_eval is None:
+            max_eval = max_iter * 5 // 4
+        defaults = dict(lr=lr, max_iter=max_iter, max_eval=max_eval, tolerance_grad=tolerance_grad,
+                        tolerance_change=tolerance_change, history_size=int(history_size), line_search_fn=line_search_fn)
+        super().__init__(params, defaults)
+        if len(self.param_groups) != 1:
+            raise ValueError("gfv.optim.LBFGS doesn't support per-parameter options (parameter groups)")
+        ps = self.param_groups[0]["params"]
+        if not ps or any((not p.is_cuda) or p.dtype != torch.float32 for p in ps):
+            raise RuntimeError("gfv.optim.LBFGS: fp32 parameters on the GPU (HIP kernels only, no CPU fallback)")
+        dev = ps[0].device
+        self._params = list(ps)
+        self.G = GradStore([str(i) for i in range(len(ps))], [p.shape for p in ps], dev)
+        n = self.n = self.G.total
+        self.flat_g = self.G.flat
+        self.flat_p = torch.zeros(n, dtype=torch.float32, device=dev)
+        self._offs = [self.G.off[str(i)] for i in range(len(ps))]
+        self._adopt()
+        mask = torch.zeros(n, dtype=torch.uint8)
+        for p, off in zip(self._params, self._offs):
+            mask[off:off + p.numel()] = 1
+        self._idx = torch.nonzero(mask).reshape(-1).to(dev)   # flat position of every real element, in parameter order
+        self.mask = mask.to(dev)
+        self.slots = int(history_size) + 1
+        self.R = 2 * self.slots + 1
+        self.S = torch.zeros(self.slots * n, dtype=torch.float32, device=dev)
+        self.Y = torch.zeros(self.slots * n, dtype=torch.float32, device=dev)
+        self.gbuf = torch.zeros(3, n, dtype=torch.float32, device=dev)   # the current gradient + the line search's live points
+        self._gcur = 0
+        self.g_prev = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.d = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.x0 = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.ring = torch.zeros(8, dtype=torch.int32, device=dev)        # head, count, accepted, -, arrival counter of dot
+        self.M = torch.zeros(self.R * self.R, dtype=torch.float64, device=dev)
+        self.delta = torch.zeros(self.R, dtype=torch.float64, device=dev)
+        self.res = torch.zeros(16, dtype=torch.float64, device=dev)
+        self.res[4] = 1.0
+        ws = int(L.load().gfv_lbfgs_workspace_doubles(self.slots, n))
+        if ws <= 0:
+            raise RuntimeError("gfv.optim.LBFGS: the library refuses this size")
+        self.partial = torch.zeros(ws, dtype=torch.float64, device=dev)
+        self.dot_ws = torch.zeros(3 * (ws // (3 * self.R + 2)), dtype=torch.float64, device=dev)
+        self.dot_out = torch.zeros(4, dtype=torch.float64, device=dev)   # g.d, max|g|, sum|g|, loss
+        L.status_mirror()
+
+    # launches -------------------------------------------------------------------------------------------------------
+    def _ingest(self, g, slot):
+        """Masked copy of the flat gradient `g` into slot `slot` + its dot with d, max|.|, sum|.| -> dot_out[0:3]."""
+        L.check(L.load().gfv_lbfgs_dot(g.data_ptr(), self.mask.data_ptr(), self.gbuf[slot].data_ptr(), self.d.data_ptr(), self.n,
+                                       self.dot_ws.data_ptr(), self.ring.data_ptr() + 16, self.dot_out.data_ptr(), L.stream_ptr()),
+                "lbfgs_dot")
+
+    def _evaluate(self, closure, slot):
+        """One closure evaluation: (loss as returned, loss, g.d, max|g|, sum|g|), the gradient in slot `slot`.  One read."""
+        with torch.enable_grad():
+            orig = closure()
+        g = self._flat_grad()
+        if g is None:
+            raise RuntimeError("gfv.optim.LBFGS: the closure left no gradient on any parameter")
+        self._ingest(g, slot)
+        if torch.is_tensor(orig) and orig.is_cuda:
+            self.dot_out[3:4].copy_(orig.detach().reshape(1))
+            r = self.dot_out.tolist()
+        else:
+            r = self.dot_out.tolist()
+            r[3] = float(orig)
+        return orig, r[3], r[0], r[1], r[2]
+
+    def _direction(self, t, mode):
+        """The four launches of a search direction from the gradient in the current slot; (g.d, max|d|, result block)."""
+        lib, st = L.load(), L.stream_ptr()
+        S, Y, g, ring = self.S.data_ptr(), self.Y.data_ptr(), self.gbuf[self._gcur].data_ptr(), self.ring.data_ptr()
+        L.check(lib.gfv_lbfgs_pair(S, Y, self.slots, self.n, ring, g, self.g_prev.data_ptr(), self.d.data_ptr(), float(t),
+                                   1 if mode == 1 else 0, st), "lbfgs_pair")
+        L.check(lib.gfv_lbfgs_multidot(S, Y, self.slots, self.n, ring, g, self.partial.data_ptr(), mode, st), "lbfgs_multidot")
+        L.check(lib.gfv_lbfgs_coef(ring, self.M.data_ptr(), self.partial.data_ptr(), self.delta.data_ptr(), self.res.data_ptr(),
+                                   self.slots, self.n, mode, st), "lbfgs_coef")
+        L.check(lib.gfv_lbfgs_combine(S, Y, self.slots, self.n, ring, g, self.delta.data_ptr(), self.d.data_ptr(),
+                                      self.res.data_ptr(), st), "lbfgs_combine")
+        r = self.res.cpu()
+        return float(r[0]), float(r[8:9].view(torch.float32)[0]), r
+
+    def _move(self, x0, t):
+        L.check(L.load().gfv_lbfgs_axpy(self.flat_p.data_ptr(), x0.data_ptr(), self.d.data_ptr(), float(t), self.mask.data_ptr(),
+                                        self.n, L.stream_ptr()), "lbfgs_axpy")
+
+    @torch.no_grad()
+    def step(self, closure):
+        from .linesearch import strong_wolfe
+        L.raise_on_status("gfv.optim.LBFGS.step")
+        self._adopt()
+        group = self.param_groups[0]
+        lr = float(group["lr"])
+        max_iter, max_eval = group["max_iter"], group["max_eval"]
+        tolerance_grad, tolerance_change = group["tolerance_grad"], group["tolerance_change"]
+        line_search_fn = group["line_search_fn"]
+        if line_search_fn not in (None, "strong_wolfe"):
+            raise RuntimeError("only 'strong_wolfe' is supported")
+        state = self.state[self._params[0]]
+        state.setdefault("func_evals", 0)
+        state.setdefault("n_iter", 0)
+
+        orig_loss, loss, _, gmax, gl1 = self._evaluate(closure, self._gcur)
+        current_evals = 1
+        state["func_evals"] += 1
+        if gmax <= tolerance_grad:
+            return orig_loss
+
+        t = state.get("t")
+        n_iter = 0
+        while n_iter < max_iter:
+            n_iter += 1
+            state["n_iter"] += 1
+            first = state["n_iter"] == 1
+            gtd, dmax, _ = self._direction(0.0 if first else t, 1 if first else 0)
+            state["prev_loss"] = prev_loss = loss
+            if first:
+                t = float(torch.tensor(min(1.0, 1.0 / gl1), dtype=torch.float32)) * lr   # (torch holds it in fp32)
+            else:
+                t = lr
+            state["t"] = t
+            if gtd > -tolerance_change:
+                break
+
+            ls_func_evals = 0
+            opt_cond = False
+            if line_search_fn is not None:
+                self.x0.copy_(self.flat_p)
+                slot_of, gmax_of, live = {0.0: self._gcur}, {0.0: gmax}, [(0.0,)]
+
+                def keep(ts):
+                    live[0] = ts
+
+                def phi(tt):
+                    used = {slot_of[x] for x in live[0] if x in slot_of}
+                    slot = next(s for s in range(3) if s not in used)
+                    for key in [key for key, v in slot_of.items() if v == slot]:
+                        del slot_of[key]
+                    self._move(self.x0, tt)
+                    _, f, gtd_new, gm, _ = self._evaluate(closure, slot)
+                    slot_of[tt], gmax_of[tt] = slot, gm
+                    return f, gtd_new
+
+                # (tolerance_change of the search is its default, as in torch's call)
+                loss, t, ls_func_evals = strong_wolfe(phi, t, loss, gtd, max_ls=max_eval - current_evals, d_norm=dmax, keep=keep)
+                self._gcur, gmax = slot_of[t], gmax_of[t]
+                self._move(self.x0, t)
+                state["t"] = t
+                opt_cond = gmax <= tolerance_grad
+            else:
+                self._move(self.flat_p, t)
+                if n_iter != max_iter:
+                    _, loss, _, gmax, _ = self._evaluate(closure, self._gcur)
+                    opt_cond = gmax <= tolerance_grad
+                    ls_func_evals = 1
+
+            current_evals += ls_func_evals
+            state["func_evals"] += ls_func_evals
+
+            if n_iter == max_iter:
+                break
+            if current_evals >= max_eval:
+                break
+            if opt_cond:
+                break
+            if dmax * abs(t) <= tolerance_change:
+                break
+            if abs(loss - prev_loss) < tolerance_change:
+                break
+        return orig_loss
+
+    # torch.optim.LBFGS's checkpoint: everything under state[0] (importer.py stores it under `optimizer0`) --------------------
+    def _unpadded(self, v):
+        return v[self._idx].detach().cpu().clone()
+
+    def _padded(self, dst, v):
+        dst.zero_()
+        dst[self._idx] = v.detach().to(device=dst.device, dtype=torch.float32).reshape(-1)
+
+    def state_dict(self):
+        state = self.state.get(self._params[0], {})
+        out = {k: state[k] for k in ("func_evals", "n_iter") if k in state}
+        if state.get("n_iter", 0) >= 1:
+            n, m1, R = self.n, self.slots, self.R
+            ring = self.ring.cpu()
+            head, count = int(ring[0]), int(ring[1])
+            M = self.M.view(R, R).cpu()
+            slots = [(head + i) % m1 for i in range(count)]
+            out["d"] = self._unpadded(self.d)
+            out["t"] = state["t"]
+            out["old_dirs"] = [self._unpadded(self.Y[s * n:(s + 1) * n]) for s in slots]
+            out["old_stps"] = [self._unpadded(self.S[s * n:(s + 1) * n]) for s in slots]
+            out["ro"] = [(1.0 / M[s, m1 + s]).clone() for s in slots]
+            out["H_diag"] = self.res[4].detach().cpu().clone()
+            out["prev_flat_grad"] = self._unpadded(self.g_prev)
+            out["prev_loss"] = state["prev_loss"]
+            out["al"] = [None] * self.param_groups[0]["history_size"]
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(self._params)))
+        return {"state": {0: out} if out else {}, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        g = sd["param_groups"][0]
+        if len(sd["param_groups"]) != 1 or len(g["params"]) != len(self._params):
+            raise ValueError("optimizer state belongs to a different parameter set")
+        src = {int(k): v for k, v in sd["state"].items()}.get(0, {})
+        for k, v in g.items():
+            if k not in ("params", "history_size"):   # (the ring was sized at construction)
+                self.param_groups[0][k] = v
+        state = self.state[self._params[0]]
+        state.clear()
+        for k in ("func_evals", "n_iter", "prev_loss"):
+            if k in src:
+                state[k] = src[k]
+        n, m1 = self.n, self.slots
+        self.ring.zero_()
+        self.M.zero_()
+        self.res.zero_()
+        H = src.get("H_diag", 1.0)
+        self.res[4] = float(H)
+        if "t" in src:
+            state["t"] = float(src["t"])
+        if "d" in src:
+            self._padded(self.d, src["d"])
+        if "prev_flat_grad" in src and src["prev_flat_grad"] is not None:
+            self._padded(self.g_prev, src["prev_flat_grad"])
+        dirs, stps = list(src.get("old_dirs", [])), list(src.get("old_stps", []))
+        if len(dirs) != len(stps):
+            raise ValueError("old_dirs and old_stps differ in length")
+        dirs, stps = dirs[-(m1 - 1):], stps[-(m1 - 1):]
+        lib, st = L.load(), L.stream_ptr()
+        for i, (y, s) in enumerate(zip(dirs, stps)):
+            self._padded(self.Y[i * n:(i + 1) * n], y)
+            self._padded(self.S[i * n:(i + 1) * n], s)
+            # the pair's rows of the dot-product matrix, by the launches that wrote them the first time: the same bits
+            L.check(lib.gfv_lbfgs_multidot(self.S.data_ptr(), self.Y.data_ptr(), m1, n, self.ring.data_ptr(),
+                                           self.gbuf[self._gcur].data_ptr(), self.partial.data_ptr(), 2, st), "lbfgs_multidot")
+            L.check(lib.gfv_lbfgs_coef(self.ring.data_ptr(), self.M.data_ptr(), self.partial.data_ptr(), self.delta.data_ptr(),
+                                       self.res.data_ptr(), m1, n, 2, st), "lbfgs_coef")

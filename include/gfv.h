@@ -861,6 +861,55 @@ int gfv_pool_assemble(const gfv_pool_args_t* args, void* stream);
 int gfv_pool_payback(const int64_t* table_host, const int64_t* table_dev, int32_t n_entries, int32_t n_attrs, int32_t x_attr,
                      const int32_t* idx, int32_t B, const float* uvp_node, int64_t N, float* raw, void* stream);
 
+/* ----------------------------------------------------------------------------------------------------------
+ * L-BFGS on flat fp32 vectors (csrc/lbfgs.hip; gfv/optim.py LBFGS): torch.optim.LBFGS's two-loop recursion carried out on
+ * coefficients over the basis {s slots, y slots, g} with the matrix M of their dot products - a fixed number of launches per
+ * search direction whatever the history size is, and no host synchronisation while it is computed.
+ *
+ * Memory the caller owns, all of it 16-byte aligned, n a multiple of 4 (the flat layout of gfv.engine.GradStore):
+ *   S, Y      float  [slots, n]      the ring of pairs, slots = history_size + 1 <= 129: the candidate pair always has a free
+ *                                    slot, so a rejected one costs the oldest pair nothing
+ *   state     int32  [8]             ring head, number of stored pairs; zero at first
+ *   M         double [R, R]          R = 2 * slots + 1: row i < slots is s of slot i, slots + i is y of slot i, 2 * slots is g
+ *   partial   double [gfv_lbfgs_workspace_doubles]   per-workgroup partial sums
+ *   delta     double [R]             the direction's coefficients
+ *   res       double [16]            result block: [0] g.d, [1] max|g|, [2] sum|g|, [3] accepted, [4] H_diag (kept from call to
+ *                                    call), [5] stored pairs, [8] (its first 4 bytes) the bits of the float max|d|
+ * PADDING IS NOT DATA: every vector handed in as g, d or a ring row must be zero in the padding slots of the flat layout.  The
+ * padding of a flat gradient holds whatever a workspace held (see the weight-gradient launches above), so a gradient enters
+ * through the masked copy of the dot launch below and nothing else.
+ * mode: 0 an iteration with a candidate pair; 1 the first iteration (no pair: head, count = 0, H_diag = 1, d = -g);
+ *       2 rebuilding M from ring rows a checkpoint filled (the candidate is accepted as it is, nothing else changes).
+ * The launches of one direction, in order:
+ *   pair      first == 0: y = g - g_prev and s = t * d into slot (head + count) % slots; always g_prev = g
+ *   multidot  candidate s, candidate y and g against every stored row, the candidate's and g, + max|g|, sum|g|: per tile of
+ *             4096 columns, sums in double
+ *   coef      one workgroup: folds the partials in a fixed order into M; accepts the candidate if y.s > 1e-10 (torch's rule:
+ *             then the ring advances and H_diag = y.s / y.y); the recursion in double; writes delta and the result block
+ *   combine   d = -sum_j delta_j b_j, the sum of an element in double and rounded once; raises res[8] to max|d|
+ * Same inputs, same bits: every sum has a fixed order, no floating-point atomics.  All return GFV_ERR_ARG - before anything
+ * touches a device - for a NULL or misaligned pointer, slots outside [2, 129], n <= 0 or not a multiple of 4, an unknown mode.
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t gfv_lbfgs_workspace_doubles(int32_t slots, int64_t n);   /* 0 for arguments the launches refuse */
+int gfv_lbfgs_pair(float* S, float* Y, int32_t slots, int64_t n, const int32_t* state, const float* g, float* g_prev,
+                   const float* d, double t, int32_t first, void* stream);
+int gfv_lbfgs_multidot(const float* S, const float* Y, int32_t slots, int64_t n, const int32_t* state, const float* g,
+                       double* partial_ws, int32_t mode, void* stream);
+int gfv_lbfgs_coef(int32_t* state, double* M, const double* partial_ws, double* delta, double* res, int32_t slots, int64_t n,
+                   int32_t mode, void* stream);
+int gfv_lbfgs_combine(const float* S, const float* Y, int32_t slots, int64_t n, const int32_t* state, const float* g,
+                      const double* delta, float* d, double* res, void* stream);
+/* out[0] = a . b, out[1] = max|a|, out[2] = sum|a| in double, in a fixed order (per-tile partials in partial_ws [3 per 4096
+ * elements], folded by the workgroup that arrives last: `counter` is an int32 the launch leaves at zero) of a MASKED a: elements
+ * whose byte of `mask` (one byte per element) is 0 count as zero - by selection, so a NaN or 1e30 there does not leak -, and
+ * the masked a is written to copy_out.  This is how a gradient enters the optimiser's own buffers.  Every pointer 16-byte
+ * aligned. */
+int gfv_lbfgs_dot(const float* a, const uint8_t* mask, float* copy_out, const float* b, int64_t n, double* partial_ws,
+                  int32_t* counter, double* out, void* stream);
+/* p = x0 + t * d (one fused multiply-add per element) where the mask byte is non-zero; p keeps its value elsewhere.  x0 == p
+ * is allowed. */
+int gfv_lbfgs_axpy(float* p, const float* x0, const float* d, double t, const uint8_t* mask, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
