@@ -11,6 +11,7 @@ from __future__ import annotations
 
 import contextlib
 import os
+import struct
 
 import torch
 
@@ -109,6 +110,8 @@ class Engine:
         self._pending = []
         self._defer_mode = os.environ.get("GFV_DEFER", "1") == "1"
         self._wt, self._wt_key, self._wt_live = {}, None, False
+        self._wt_desc, self._wt_n, self._wt_max = None, 0, (0, 0)   # descriptor table of the batched transpose (prepare_transposes)
+        self._last_gn = False   # simulator_bwd: the GnBlock being differentiated is the last one of the backward
         self.mp = message_passing_num
         self.mode = _MODE[integrator]
         self.smooth = 1 if ncn_smooth else 0
@@ -410,9 +413,8 @@ class Engine:
         lib = L.load()
         key = self._pkey(P)
         if self._wt_key != key:
-            import ctypes as C
             rows = []
-            self._retired.append((self._wt, getattr(self, "_wt_desc", None)))
+            self._retired.append((self._wt, self._wt_desc))
             self._wt = {}
             dev = next(iter(P.values())).device
             for n, W in P.items():
@@ -439,7 +441,6 @@ class Engine:
                     out = _empty(dev, c, r)
                     rows.append((W.data_ptr(), out.data_ptr(), r, c, c, 0))
                     self._wt[(W.data_ptr(), False)] = out
-            import struct
             blob = b"".join(struct.pack("<QQiiii", a, b, r, c, ld, ldo) for a, b, r, c, ld, ldo in rows)
             self._wt_desc = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
             self._wt_n = len(rows)
@@ -567,24 +568,17 @@ class Engine:
         s0, s1, s2 = (gs[0], gs[1], gs[2]) if have else (None, None, None)
         if not ln and (gadd is not None or g_add is not None):
             s0 = None   # slot 0 describes the prologue RESULT (= g3 with LayerNorm); without it the weight gradient reads G
-        # (narrow raw inputs - the encoders' x [N,12] / edge_attr [E,15] with geometric columns at mesh-spacing scale - get
-        # per-column scales in the split-fp16 weight gradient; 128-wide latent segments are O(1) and go unscaled)
-        tiles = [self._tile(gz1, 128, sg, in_add=sv["in_add"] if i == 0 else None, gscale=s2,
-                            a_op=L.DW_COLSCALE if sg.width <= 16 else 0) for i, sg in enumerate(sv["segs"])]
+        tiles = self._first_layer_tiles(sv, gz1, s2)
         tiles.append(self._tile(gz2, 128, Seg(sv["z1"]), a_op=1, gscale=s1))
         tiles.append(self._tile(g3, nout, Seg(sv["z2"]), a_op=1, ldg=(G.stride(0) if g_ld is None else g_ld) if not ln else None,
                                 gscale=s0))
         def side():
             # all weight gradients of the MLP in one launch, all their reductions (slab partials -> the gradient block,
             # per-tile LayerNorm partials -> dgamma | dbeta) in one more
-            wptr, slabs, blen, _ = self._dw_block(
-                grads, [(names[0], names[1], len(sv["segs"])), (names[2], names[3], 1), (names[4], names[5], 1)], tiles, M,
-                reduce=False)
-            off0, _ = grads.block(names[0], names[5])
-            pieces = [dict(partial=wptr, out=grads.flat.data_ptr() + 4 * off0, n_chunks=slabs, chunk_stride=blen, rows=1, cols=blen)]
+            lay = [(names[0], names[1], len(sv["segs"])), (names[2], names[3], 1), (names[4], names[5], 1)]
+            pieces = [self._slab_piece(grads, lay, self._dw_block(grads, lay, tiles, M, reduce=False))]
             if ln:
-                pieces.append(dict(partial=part, out=self._gview2(grads, names[6], names[7]), n_chunks=tiles_n, chunk_stride=256,
-                                   rows=1, cols=256))
+                pieces.append(self._ln_piece(part, tiles_n, grads, names[6], names[7]))
             ops.reduce_multi(pieces)
         self.defer(side, gz1, gz2, g3, G, part, gs, sv["z1"], sv["z2"], sv["in_add"], *[sg.t for sg in sv["segs"]],
                    *[sg.idx for sg in sv["segs"]])
@@ -597,8 +591,7 @@ class Engine:
         dev = G.device
         lib = L.load()
         nwg = lib.gfv_rowtile_dw_partials_m(M)
-        FL = L.DW_FUSED_FLOATS
-        dwp = _empty(dev, nwg, FL)
+        dwp = _empty(dev, nwg, L.DW_FUSED_FLOATS)
         gz1 = _empty(dev, M, 128)
         gs = _empty(dev, 3, ops.gscale_ld(M))
         if outs is None:
@@ -614,29 +607,58 @@ class Engine:
             return False
         ops.rowtile_chain(M, [Seg(G)], layers, outs, **kw)
         segs = sv["segs"]
-
-        base = dwp.data_ptr()
-        piece = lambda off, out, cols: dict(partial=base + 4 * off, out=out, n_chunks=nwg, chunk_stride=FL, rows=1, cols=cols)
-        fused_pieces = [piece(16384 + 128, self._gview2(grads, names[2], names[3]), 16384 + 128),   # dW2 | db2
-                        piece(0, self._gview2(grads, names[4], names[5]), 16384 + 128),             # dW3 | db3
-                        piece(2 * 16384 + 256, self._gview2(grads, names[6], names[7]), 256)]       # dgamma | dbeta
-        keep = (dwp, gz1, gs, sv["in_add"], *[sg.t for sg in segs], *[sg.idx for sg in segs])
+        fused_pieces = self._fused_pieces(dwp, nwg, grads, names)
 
         def side():
             lay = [(names[0], names[1], len(segs))]
-            tiles = [self._tile(gz1, 128, sg, in_add=sv["in_add"] if i == 0 else None, gscale=gs[2],
-                                a_op=L.DW_COLSCALE if sg.width <= 16 else 0) for i, sg in enumerate(segs)]
-            w1, slabs1, blen1, _ = self._dw_block(grads, lay, tiles, M, reduce=False)
-            off0, _ = grads.block(names[0], names[1])
-            ops.reduce_multi([dict(partial=w1, out=grads.flat.data_ptr() + 4 * off0, n_chunks=slabs1, chunk_stride=blen1, rows=1,
-                                   cols=blen1)] + fused_pieces)
-        self.defer(side, *keep)
+            first = self._dw_block(grads, lay, self._first_layer_tiles(sv, gz1, gs[2]), M, reduce=False)
+            ops.reduce_multi([self._slab_piece(grads, lay, first)] + fused_pieces)
+        self.defer(side, dwp, gz1, gs, sv["in_add"], *[sg.t for sg in segs], *[sg.idx for sg in segs])
         return True
 
     @staticmethod
     def _gview2(grads, n0, n1):
         off, length = grads.block(n0, n1)
         return grads.flat[off:off + length]
+
+    @staticmethod
+    def _piece(partial, out, n_chunks, chunk_stride, cols, rows=1, ld_out=None):
+        """One piece of `ops.reduce_multi`: out [rows, cols] (row stride ld_out, default cols) = the sum of n_chunks blocks that lie
+        chunk_stride floats apart from `partial` on, rows of `cols` floats each (ld_in: reduce_multi's default, cols)."""
+        p = dict(partial=partial, out=out, n_chunks=n_chunks, chunk_stride=chunk_stride, rows=rows, cols=cols)
+        if ld_out is not None:
+            p["ld_out"] = ld_out
+        return p
+
+    def _ln_piece(self, part, n_rows, grads, gamma, beta):
+        """Per-tile LayerNorm partials [n_rows, 2, 128] of a chain launch -> the dgamma | dbeta block."""
+        return self._piece(part, self._gview2(grads, gamma, beta), n_rows, 256, 256)
+
+    def _fused_pieces(self, dwp, nwg, grads, names):
+        """The per-workgroup blocks a chain launch with fused weight gradients left in `dwp` (layout: lib.DW_FUSED_*) -> the
+        gradients of the MLP's second and third Linear and of its LayerNorm."""
+        base, FL, WB = dwp.data_ptr(), L.DW_FUSED_FLOATS, L.DW_FUSED_WB
+        return [self._piece(base + 4 * L.DW_FUSED_OFF_W2, self._gview2(grads, names[2], names[3]), nwg, FL, WB),
+                self._piece(base + 4 * L.DW_FUSED_OFF_W3, self._gview2(grads, names[4], names[5]), nwg, FL, WB),
+                self._piece(base + 4 * L.DW_FUSED_OFF_LN, self._gview2(grads, names[6], names[7]), nwg, FL, 256)]
+
+    @staticmethod
+    def _layers_block(grads, layers):
+        """(offset, length) of the contiguous gradient block of a `_dw_block` layers list."""
+        last = layers[-1]
+        return grads.block(layers[0][0], last[1] if last[1] is not None else last[0])
+
+    def _slab_piece(self, grads, layers, slabs):
+        """slabs: what `_dw_block(grads, layers, ..., reduce=False)` returned -> its slab partials summed into that gradient block."""
+        wptr, n, blen, _ = slabs
+        return self._piece(wptr, grads.flat.data_ptr() + 4 * self._layers_block(grads, layers)[0], n, blen, blen)
+
+    def _first_layer_tiles(self, sv, gz1, scale):
+        """Weight-gradient tiles of an MLP's first Linear, one per saved input segment.  (Narrow raw inputs - the encoders' x [N,12] /
+        edge_attr [E,15] with geometric columns at mesh-spacing scale - get per-column scales in the split-fp16 weight gradient;
+        128-wide latent segments are O(1) and go unscaled.)"""
+        return [self._tile(gz1, 128, sg, in_add=sv["in_add"] if i == 0 else None, gscale=scale,
+                           a_op=L.DW_COLSCALE if sg.width <= 16 else 0) for i, sg in enumerate(sv["segs"])]
 
     @staticmethod
     def _tile(G, n_out, seg, *, a_op=0, a_gamma=None, a_beta=None, in_add=None, ldg=None, g_offset=0, gscale=None):
@@ -655,9 +677,7 @@ class Engine:
         reduce=False leaves the slab partials in the workspace at float offset `ws_offset` and returns
         (pointer, slabs, floats per slab, workspace floats used) for a caller that folds several reductions into one launch."""
         lib = L.load()
-        first = layers[0][0]
-        last = layers[-1][1] if layers[-1][1] is not None else layers[-1][0]
-        off0, blen = grads.block(first, last)
+        off0, blen = self._layers_block(grads, layers)
         ct = (L.DwTile * 6)()
         ti = 0
         for li, (wname, bname, nt) in enumerate(layers):
@@ -701,22 +721,14 @@ class Engine:
         partials) folded into the same launch."""
         lib = L.load()
         dev = grads.flat.device
-        needs = []
-        for j in jobs:
-            first = j["layers"][0][0]
-            last = j["layers"][-1][1] if j["layers"][-1][1] is not None else j["layers"][-1][0]
-            blen = grads.block(first, last)[1]
-            needs.append((lib.gfv_dw_multi_workspace_floats(j["M"], len(j["tiles"]), blen) + 3) // 4 * 4)
+        needs = [(lib.gfv_dw_multi_workspace_floats(j["M"], len(j["tiles"]), self._layers_block(grads, j["layers"])[1]) + 3) // 4 * 4
+                 for j in jobs]
         self._workspace(sum(needs) + 8, dev)
         out, off = [], 0
         for j, need in zip(jobs, needs):
-            first = j["layers"][0][0]
-            last = j["layers"][-1][1] if j["layers"][-1][1] is not None else j["layers"][-1][0]
-            wptr, slabs, blen, used = self._dw_block(grads, j["layers"], j["tiles"], j["M"], row0s=j.get("row0s"), reduce=False,
-                                                     ws_offset=off)
-            assert used <= need
-            off0, _ = grads.block(first, last)
-            out.append(dict(partial=wptr, out=grads.flat.data_ptr() + 4 * off0, n_chunks=slabs, chunk_stride=blen, rows=1, cols=blen))
+            slabs = self._dw_block(grads, j["layers"], j["tiles"], j["M"], row0s=j.get("row0s"), reduce=False, ws_offset=off)
+            assert slabs[3] <= need
+            out.append(self._slab_piece(grads, j["layers"], slabs))
             off += need
         out += list(pieces)
         for k in range(0, len(out), 12):   # (gfv_reduce_multi takes 12 pieces)
@@ -782,6 +794,45 @@ class Engine:
             self._etmp = (e, n)
         return self._etmp
 
+    def _edge_gather_adjoint(self, gz1, pl, Wabt):
+        """Adjoint of the gathers (W1a nb)[s], (W1b nb)[r] of the factored EdgeBlock: per-side scatter of dz1 to the nodes (in the
+        prologue of the launch - `csr_fuse & 4` - or as two launches), then ONE node-level GEMM.  -> (g_nb, G_s, G_r), [N,128] each."""
+        N, dev = pl.N, gz1.device
+        g_nb = _empty(dev, N, 128)
+        if self.csr_fuse and (self._fuse_mask & 4):
+            G_s, G_r = _empty(dev, N, 128), _empty(dev, N, 128)
+            ops.rowtile_chain(N, [Seg(gz1, csr=(pl.s_rowptr, pl.s_col), save=G_s), Seg(gz1, csr=(pl.r_rowptr, pl.r_col), save=G_r)],
+                              [LayerSpec(Wabt)], [g_nb])
+        else:
+            G_s = ops.seg_gather_sum(gz1, pl.s_rowptr, pl.s_col, N)
+            G_r = ops.seg_gather_sum(gz1, pl.r_rowptr, pl.r_col, N)
+            ops.rowtile_chain(N, [Seg(G_s), Seg(G_r)], [LayerSpec(Wabt)], [g_nb])
+        return g_nb, G_s, G_r
+
+    def _edge_dw(self, grads, names, M, N, tilesE, G_s, G_r, nb, before=(), after=()):
+        """The weight gradients of the factored EdgeBlock MLP that its chain launch did not form: `tilesE` over the M edge rows (the
+        first Linear's c block; behind an unfused chain the second and third Linear too) and the node-level pair of W1a / W1b.
+        Slab partials are laid out like small stand-in blocks ([W1c | b1 | W2 | b2 | W3 | b3] and [W1a | W1b]), in two regions of
+        the workspace; ONE launch then reduces every piece straight into its place of the real gradient block (W1c / W1ab are
+        column blocks of W1 [128, 384]) together with the caller's pieces `before` / `after` it."""
+        lib = L.load()
+        dev = grads.flat.device
+        tmpE, tmpN = self._edge_tmp(dev)
+        layE, layN = [("W1c", "b1", 1), ("W2", "b2", 1), ("W3", "b3", 1)][:len(tilesE)], [("W1ab", None, 2)]
+        self._workspace(lib.gfv_dw_multi_workspace_floats(M, len(tilesE), self._layers_block(tmpE, layE)[1])
+                        + lib.gfv_dw_multi_workspace_floats(N, 2, self._layers_block(tmpN, layN)[1]) + 8, dev)   # both regions, once
+        w1, slabs1, blen1, used = self._dw_block(tmpE, layE, tilesE, M, reduce=False)
+        w2, slabs2, blen2, _ = self._dw_block(tmpN, layN, [self._tile(G_s, 128, Seg(nb)), self._tile(G_r, 128, Seg(nb))], N,
+                                              reduce=False, ws_offset=used)
+        assert w2 == w1 + 4 * used
+        gW1 = grads.view(names[0])
+        ob, lb = tmpE.block("b1", layE[-1][1])   # b1 [| W2 | b2 | W3 | b3]: contiguous in the real gradient block as well
+        assert lb == grads.block(names[1], names[2 * len(tilesE) - 1])[1]
+        ops.reduce_multi([*before,
+                          self._piece(w1, gW1.data_ptr() + 4 * 256, slabs1, blen1, 128, rows=128, ld_out=384),
+                          self._piece(w1 + 4 * ob, grads.flat.data_ptr() + 4 * grads.off[names[1]], slabs1, blen1, lb),
+                          self._piece(w2, gW1.data_ptr(), slabs2, blen2, 256, rows=128, ld_out=384), *after])
+
     def edge_bwd_factored(self, P, sv, G, grads, pl, gadd):
         """Adjoint of the factored EdgeBlock MLP.  Returns (grad wrt nb [N,128], grad wrt e [E,128] incl. residual)."""
         prefix, M, N = sv["prefix"], sv["M"], pl.N
@@ -805,43 +856,13 @@ class Engine:
                                  ln_partial=part, gadd=gadd[0], gadd_s=gadd[1], gadd_r=gadd[2], gscale=gs, in_stats=sv.get("stats"))
         tiles_n = ops.last_ln_rows()
         s0, s1, s2 = (gs[0], gs[1], gs[2]) if have else (None, None, None)
-        # adjoint of the gathers (W1a nb)[s], (W1b nb)[r]: per-side scatter of dz1 to the nodes, then ONE node-level GEMM
-        g_nb = _empty(dev, N, 128)
-        if self.csr_fuse and (self._fuse_mask & 4):
-            G_s, G_r = _empty(dev, N, 128), _empty(dev, N, 128)
-            ops.rowtile_chain(N, [Seg(gz1, csr=(pl.s_rowptr, pl.s_col), save=G_s), Seg(gz1, csr=(pl.r_rowptr, pl.r_col), save=G_r)],
-                              [LayerSpec(Wabt)], [g_nb])
-        else:
-            G_s = ops.seg_gather_sum(gz1, pl.s_rowptr, pl.s_col, N)
-            G_r = ops.seg_gather_sum(gz1, pl.r_rowptr, pl.r_col, N)
-            ops.rowtile_chain(N, [Seg(G_s), Seg(G_r)], [LayerSpec(Wabt)], [g_nb])
+        g_nb, G_s, G_r = self._edge_gather_adjoint(gz1, pl, Wabt)
         nb = sv["nb"]
         def side():
-            # slab partials are laid out like small stand-in blocks ([W1c | b1 | W2 | b2 | W3 | b3] and [W1a | W1b]), in two
-            # regions of the workspace; ONE launch then reduces every piece straight into its place of the real gradient
-            # block (W1c / W1ab are column blocks of W1 [128, 384]) together with the per-tile LayerNorm partials
-            tmpE, tmpN = self._edge_tmp(dev)
-            gW1 = grads.view(names[0])
-            lib = L.load()
-            self._workspace(lib.gfv_dw_multi_workspace_floats(M, 3, tmpE.block("W1c", "b3")[1])
-                            + lib.gfv_dw_multi_workspace_floats(N, 2, tmpN.block("W1ab", "W1ab")[1]) + 8, dev)   # both regions, once
-            w1, slabs1, blen1, used = self._dw_block(tmpE, [("W1c", "b1", 1), ("W2", "b2", 1), ("W3", "b3", 1)],
-                                                     [self._tile(gz1, 128, Seg(e), gscale=s2),
-                                                      self._tile(gz2, 128, Seg(sv["z1"]), a_op=1, gscale=s1),
-                                                      self._tile(g3, 128, Seg(sv["z2"]), a_op=1, gscale=s0)], M, reduce=False)
-            w2, slabs2, blen2, _ = self._dw_block(tmpN, [("W1ab", None, 2)],
-                                                  [self._tile(G_s, 128, Seg(nb)), self._tile(G_r, 128, Seg(nb))], N,
-                                                  reduce=False, ws_offset=used)
-            assert w2 == w1 + 4 * used
-            off, length = grads.block(names[1], names[5])
-            o2, l2 = tmpE.block("b1", "b3")
-            assert l2 == length
-            ops.reduce_multi([
-                dict(partial=w1, out=gW1.data_ptr() + 4 * 256, n_chunks=slabs1, chunk_stride=blen1, rows=128, cols=128, ld_out=384),
-                dict(partial=w1 + 4 * o2, out=grads.flat.data_ptr() + 4 * off, n_chunks=slabs1, chunk_stride=blen1, rows=1, cols=l2),
-                dict(partial=w2, out=gW1.data_ptr(), n_chunks=slabs2, chunk_stride=blen2, rows=128, cols=256, ld_out=384),
-                dict(partial=part, out=self._gview2(grads, names[6], names[7]), n_chunks=tiles_n, chunk_stride=256, rows=1,
-                     cols=256)])
+            self._edge_dw(grads, names, M, N, [self._tile(gz1, 128, Seg(e), gscale=s2),
+                                               self._tile(gz2, 128, Seg(sv["z1"]), a_op=1, gscale=s1),
+                                               self._tile(g3, 128, Seg(sv["z2"]), a_op=1, gscale=s0)], G_s, G_r, nb,
+                          after=[self._ln_piece(part, tiles_n, grads, names[6], names[7])])
         self.defer(side, gz1, gz2, g3, G_s, G_r, nb, e, part, gs, sv["z1"], sv["z2"])
         return g_nb, g_e_in
 
@@ -857,8 +878,7 @@ class Engine:
         lib = L.load()
         nwg = lib.gfv_rowtile_dw_partials_m(M)
         lean = sv["z2"] is None   # recompute form: the forward kept z1 only
-        FL = L.DW_FUSED_FLOATS
-        dwp = _empty(dev, nwg, FL)
+        dwp = _empty(dev, nwg, L.DW_FUSED_FLOATS)
         gz1, g_e_in = _empty(dev, M, 128), _empty(dev, M, 128)
         layers = [LayerSpec(W3t, None, L.OP_MUL_DGELU, aux=sv["z2"]), LayerSpec(W2t, None, L.OP_MUL_DGELU, save=gz1, aux=sv["z1"]),
                   LayerSpec(W1ct)]
@@ -869,41 +889,13 @@ class Engine:
         if not ops.rowtile_chain(M, [Seg(G)], layers, [g_e_in], query_fused=True, **kw):
             return None
         ops.rowtile_chain(M, [Seg(G)], layers, [g_e_in], **kw)
-        # adjoint of the gathers (W1a nb)[s], (W1b nb)[r]: per-side scatter of dz1 to the nodes, then ONE node-level GEMM
-        g_nb = _empty(dev, N, 128)
-        if self.csr_fuse and (self._fuse_mask & 4):
-            G_s, G_r = _empty(dev, N, 128), _empty(dev, N, 128)
-            ops.rowtile_chain(N, [Seg(gz1, csr=(pl.s_rowptr, pl.s_col), save=G_s), Seg(gz1, csr=(pl.r_rowptr, pl.r_col), save=G_r)],
-                              [LayerSpec(Wabt)], [g_nb])
-        else:
-            G_s = ops.seg_gather_sum(gz1, pl.s_rowptr, pl.s_col, N)
-            G_r = ops.seg_gather_sum(gz1, pl.r_rowptr, pl.r_col, N)
-            ops.rowtile_chain(N, [Seg(G_s), Seg(G_r)], [LayerSpec(Wabt)], [g_nb])
+        g_nb, G_s, G_r = self._edge_gather_adjoint(gz1, pl, Wabt)
         nb = sv["nb"]
 
         def side():
-            tmpE, tmpN = self._edge_tmp(dev)
-            gW1 = grads.view(names[0])
-            base = dwp.data_ptr()
-            piece = lambda off, out, rows, cols, ld_out=None: dict(partial=base + 4 * off, out=out, n_chunks=nwg, chunk_stride=FL,
-                                                                   rows=rows, cols=cols, ld_in=cols, ld_out=cols if ld_out is None else ld_out)
-            pieces = [piece(16384 + 128, self._gview2(grads, names[2], names[3]), 1, 16384 + 128),   # dW2 | db2
-                      piece(0, self._gview2(grads, names[4], names[5]), 1, 16384 + 128),             # dW3 | db3
-                      piece(2 * 16384 + 256, self._gview2(grads, names[6], names[7]), 1, 256)]       # dgamma | dbeta
-            # the first layer's c block by the weight-gradient kernel (one tile over the E rows): slab partials laid out
-            # like a stand-in [W1c | b1] block
-            lay = [("W1c", "b1", 1)]
-            self._workspace(lib.gfv_dw_multi_workspace_floats(M, 1, tmpE.block("W1c", "b1")[1])
-                            + lib.gfv_dw_multi_workspace_floats(N, 2, tmpN.block("W1ab", "W1ab")[1]) + 8, dev)   # both regions, once
-            w1, slabs1, blen1, used = self._dw_block(tmpE, lay, [self._tile(gz1, 128, Seg(e), gscale=gs[2])], M, reduce=False)
-            ob1, lb1 = tmpE.block("b1", "b1")
-            pieces += [dict(partial=w1, out=gW1.data_ptr() + 4 * 256, n_chunks=slabs1, chunk_stride=blen1, rows=128, cols=128, ld_out=384),
-                       dict(partial=w1 + 4 * ob1, out=grads.view(names[1]), n_chunks=slabs1, chunk_stride=blen1, rows=1, cols=128)]
-            w2, slabs2, blen2, _ = self._dw_block(tmpN, [("W1ab", None, 2)],
-                                                  [self._tile(G_s, 128, Seg(nb)), self._tile(G_r, 128, Seg(nb))], N, reduce=False,
-                                                  ws_offset=used)
-            pieces.append(dict(partial=w2, out=gW1.data_ptr(), n_chunks=slabs2, chunk_stride=blen2, rows=128, cols=256, ld_out=384))
-            ops.reduce_multi(pieces)
+            # the first layer's c block by the weight-gradient kernel (one tile over the E rows)
+            self._edge_dw(grads, names, M, N, [self._tile(gz1, 128, Seg(e), gscale=gs[2])], G_s, G_r, nb,
+                          before=self._fused_pieces(dwp, nwg, grads, names))
         self.defer(side, dwp, gz1, e, G_s, G_r, nb, gs)
         return g_nb, g_e_in
 
@@ -925,7 +917,7 @@ class Engine:
             g_nb = ops.seg_gather_sum(gnb2.view(2 * E, 128), pl.n_rowptr, pl.n_col_edge2, N)
         ops.seg_gather_sum(g_nb, pl.n_rowptr, pl.n_col_node, N, out=g_x_in, accumulate=True)
         # the block's weight gradients: one fork (the last block's may go to the main stream: GFV_TAIL_MAIN >= 3)
-        last = self._defer_mode and getattr(self, "_last_gn", False)
+        last = self._defer_mode and self._last_gn
         tail_main, tail_split = self._tail_cfg(pl)
         self.flush(on_main=last and tail_main >= 3, split=tail_split if last else 0)
         return g_x_in, g_e_in
@@ -1012,6 +1004,17 @@ class Engine:
                                                  out.data_ptr(), L.stream_ptr()), "reduce_partials_seg")
         return out, pl.gunit_ptr
 
+    def _trans_group_alone(self, grads, job, pieces):
+        """One gradient group of a Transolver block with launches of its own (GFV_TRANS_REDUCE_MERGE=0): a weight-gradient job alone
+        reduces inside its launch; with further pieces its slab partials and they share one reduction launch; pieces alone are one."""
+        if job is None:
+            ops.reduce_multi(pieces)
+        elif not pieces:
+            self._dw_block(grads, job["layers"], job["tiles"], job["M"], row0s=job.get("row0s"))
+        else:
+            slabs = self._dw_block(grads, job["layers"], job["tiles"], job["M"], row0s=job.get("row0s"), reduce=False)
+            ops.reduce_multi([self._slab_piece(grads, job["layers"], slabs)] + pieces)
+
     def trans_bwd(self, P, sv, g_out, grads, pl, g_add=None):
         """g_add: optional addend of the incoming gradient (g_out + g_add is the gradient); the sum is formed in the
         prologue of the first launch and kept (no separate elementwise pass)."""
@@ -1028,7 +1031,7 @@ class Engine:
         g_z = _empty(dev, N, 256)
         g_sum = _empty(dev, N, 128) if g_add is not None else None
         gs = _empty(dev, 3, ops.gscale_ld(N))
-        tiles = ops.rowtile_tiles(N)
+        ln_n = ops.rowtile_tiles(N)
         part = _empty(dev, ops.ln_rows(N), 2, 128)
         g_fx1, g_out_x = _empty(dev, N, 128), _empty(dev, N, 128)
         gam2, bet2 = P[f"{prefix}.ln_2.weight"], P[f"{prefix}.ln_2.bias"]
@@ -1039,7 +1042,7 @@ class Engine:
                                    gam2, g_z, g_fx1, g_out_x, part, gs[0]))
         if fused:
             have = True
-            tiles = lib.gfv_trans_mlp_ln_rows(N)   # (one ln_partial row per 64 rows, per 32 from the small-tile form)
+            ln_n = lib.gfv_trans_mlp_ln_rows(N)   # (one ln_partial row per 64 rows, per 32 from the small-tile form)
         else:
             have = ops.rowtile_chain(N, [Seg(g_out)], [LayerSpec(self._T(Wpost), None, L.OP_MUL_DGELU, aux=z)],
                                      [(g_z, 256), (g_z.data_ptr() + 512, 256)], in_add=g_add, in_save=g_sum, gscale=gs)
@@ -1047,49 +1050,38 @@ class Engine:
         if g_add is not None:
             g_out = g_sum
         g_post = g_out
+        # The block's parameter gradients come in six groups: a weight-gradient job (as `_dw_jobs` takes them), further reduction
+        # pieces, the tensors the side queue must keep alive.  Merged (the default): the block's four weight-gradient launches,
+        # then ONE reduction launch for all of their slab partials, the LayerNorm partials and the attention / slice-projection
+        # partials (11 pieces; was six reduction launches).  GFV_TRANS_REDUCE_MERGE=0: every group by itself, where it arises
+        # (`_trans_group_alone`: another summation order).
         merge = self._trans_reduce_merge
-        jobs, extra, keep = [], [], [g_post, z, gs]
-        if merge:
-            jobs.append(dict(layers=[(f"{prefix}.mlp.linear_post.weight", f"{prefix}.mlp.linear_post.bias", 2)],
-                             tiles=[self._tile(g_post, 128, zs, a_op=1, gscale=s_post) for zs in zsegs], M=N))
-        else:
-            self.defer(lambda: self._dw_block(grads, [(f"{prefix}.mlp.linear_post.weight", f"{prefix}.mlp.linear_post.bias", 2)],
-                                              [self._tile(g_post, 128, zs, a_op=1, gscale=s_post) for zs in zsegs], N), g_post, z, gs)
+        jobs, extra, keep = [], [], []
+
+        def group(job, pieces, *alive):
+            if merge:
+                if job is not None:
+                    jobs.append(job)
+                extra.extend(pieces)
+                keep.extend(alive)
+            else:
+                self.defer(lambda: self._trans_group_alone(grads, job, pieces), *alive)
+        group(dict(layers=[(f"{prefix}.mlp.linear_post.weight", f"{prefix}.mlp.linear_post.bias", 2)],
+                   tiles=[self._tile(g_post, 128, zs, a_op=1, gscale=s_post) for zs in zsegs], M=N), [], g_post, z, gs)
         # linear_pre behind LayerNorm ln_2
         if not fused:
             ops.rowtile_chain(N, [Seg(g_z, width=128, ld=256), Seg(g_z, width=128, ld=256, offset=128)],
                               [LayerSpec(self._T(Wpre))], [g_fx1], fin_op=L.FIN_LNBWD, fin_gamma=gam2, fin_aux=fx1,
                               ln_partial=part, res=[g_out])
-        def side_pre():
-            wn, bn = f"{prefix}.mlp.linear_pre.0.weight", f"{prefix}.mlp.linear_pre.0.bias"
-            wptr, slabs, blen, _ = self._dw_block(
-                grads, [(wn, bn, 2)],
-                [self._tile(g_z, 128, Seg(fx1), a_op=2, a_gamma=gam2, a_beta=bet2, ldg=256, g_offset=128 * h) for h in range(2)],
-                N, row0s=[0, 128], reduce=False)
-            off0, _ = grads.block(wn, bn)
-            ops.reduce_multi([
-                dict(partial=wptr, out=grads.flat.data_ptr() + 4 * off0, n_chunks=slabs, chunk_stride=blen, rows=1, cols=blen),
-                dict(partial=part, out=self._gview2(grads, f"{prefix}.ln_2.weight", f"{prefix}.ln_2.bias"), n_chunks=tiles,
-                     chunk_stride=256, rows=1, cols=256)])
-        if merge:
-            jobs.append(dict(layers=[(f"{prefix}.mlp.linear_pre.0.weight", f"{prefix}.mlp.linear_pre.0.bias", 2)],
-                             tiles=[self._tile(g_z, 128, Seg(fx1), a_op=2, a_gamma=gam2, a_beta=bet2, ldg=256, g_offset=128 * h)
-                                    for h in range(2)], M=N, row0s=[0, 128]))
-            extra.append(dict(partial=part, out=self._gview2(grads, f"{prefix}.ln_2.weight", f"{prefix}.ln_2.bias"), n_chunks=tiles,
-                              chunk_stride=256, rows=1, cols=256))
-            keep += [g_z, fx1, part]
-        else:
-            self.defer(side_pre, g_z, fx1, part)
+        group(dict(layers=[(f"{prefix}.mlp.linear_pre.0.weight", f"{prefix}.mlp.linear_pre.0.bias", 2)],
+                   tiles=[self._tile(g_z, 128, Seg(fx1), a_op=2, a_gamma=gam2, a_beta=bet2, ldg=256, g_offset=128 * h) for h in range(2)],
+                   M=N, row0s=[0, 128]),
+              [self._ln_piece(part, ln_n, grads, f"{prefix}.ln_2.weight", f"{prefix}.ln_2.bias")], g_z, fx1, part)
         # to_out
         if not fused:
             ops.rowtile_chain(N, [Seg(g_fx1)], [LayerSpec(self._T(P[f"{a}.to_out.0.weight"]))], [g_out_x])
-        if merge:
-            jobs.append(dict(layers=[(f"{a}.to_out.0.weight", f"{a}.to_out.0.bias", 1)],
-                             tiles=[self._tile(g_fx1, 128, Seg(sv["out_x"]))], M=N))
-            keep += [g_fx1, sv["out_x"]]
-        else:
-            self.defer(lambda: self._dw_block(grads, [(f"{a}.to_out.0.weight", f"{a}.to_out.0.bias", 1)],
-                                              [self._tile(g_fx1, 128, Seg(sv["out_x"]))], N), g_fx1, sv["out_x"])
+        group(dict(layers=[(f"{a}.to_out.0.weight", f"{a}.to_out.0.bias", 1)], tiles=[self._tile(g_fx1, 128, Seg(sv["out_x"]))], M=N),
+              [], g_fx1, sv["out_x"])
         # de-slice / attention / slice
         w, batch = sv["w"], pl.batch
         fused_post = self._slice_fuse
@@ -1108,15 +1100,9 @@ class Engine:
                                             P[f"{a}.to_v.weight"].data_ptr(), sv["token"].data_ptr(), sv["norm"].data_ptr(),
                                             sv["attn"].data_ptr(), g_raw.data_ptr(), g_norm.data_ptr(), dwp.data_ptr(), st),
                 "slice_attention_bwd")
-        def side_qkv():   # parameter gradients only: off the critical path; one launch, straight into the three tensors
-            ops.reduce_multi([dict(partial=dwp.data_ptr() + 4 * 256 * i, out=grads.view(f"{a}.{nm}.weight"), n_chunks=B * 8,
-                                   chunk_stride=768, rows=1, cols=256) for i, nm in enumerate(("to_q", "to_k", "to_v"))])
-        if merge:
-            extra += [dict(partial=dwp.data_ptr() + 4 * 256 * i, out=grads.view(f"{a}.{nm}.weight"), n_chunks=B * 8,
-                           chunk_stride=768, rows=1, cols=256) for i, nm in enumerate(("to_q", "to_k", "to_v"))]
-            keep.append(dwp)
-        else:
-            self.defer(side_qkv, dwp)
+        # (parameter gradients only: off the critical path; one launch, straight into the three tensors)
+        group(None, [self._piece(dwp.data_ptr() + 4 * 256 * i, grads.view(f"{a}.{nm}.weight"), B * 8, 768, 256)
+                     for i, nm in enumerate(("to_q", "to_k", "to_v"))], dwp)
         g_fx_mid = _empty(dev, N, 128)
         nblk = lib.gfv_slice_softmax_bwd_blocks(N)
         sp = _empty(dev, nblk, 552)
@@ -1136,18 +1122,9 @@ class Engine:
             L.check(lib.gfv_slice_softmax_bwd(sv["x_mid"].data_ptr(), P[f"{a}.in_project_slice.weight"].data_ptr(),
                                               P[f"{a}.in_project_slice.bias"].data_ptr(), temp.data_ptr(), w.data_ptr(),
                                               gw.data_ptr(), g_x_mid.data_ptr(), sp.data_ptr(), N, st), "slice_softmax_bwd")
-        def side_slice():
-            ops.reduce_multi([dict(partial=sp.data_ptr() + 4 * o, out=grads.view(nm), n_chunks=nblk, chunk_stride=552, rows=1,
-                                   cols=c)
-                              for o, c, nm in ((0, 512, f"{a}.in_project_slice.weight"), (512, 32, f"{a}.in_project_slice.bias"),
-                                               (544, 8, f"{a}.graph_temperature"))])
-        if merge:
-            extra += [dict(partial=sp.data_ptr() + 4 * o, out=grads.view(nm), n_chunks=nblk, chunk_stride=552, rows=1, cols=c)
-                      for o, c, nm in ((0, 512, f"{a}.in_project_slice.weight"), (512, 32, f"{a}.in_project_slice.bias"),
-                                       (544, 8, f"{a}.graph_temperature"))]
-            keep.append(sp)
-        else:
-            self.defer(side_slice, sp)
+        group(None, [self._piece(sp.data_ptr() + 4 * o, grads.view(nm), nblk, 552, c)
+                     for o, c, nm in ((0, 512, f"{a}.in_project_slice.weight"), (512, 32, f"{a}.in_project_slice.bias"),
+                                      (544, 8, f"{a}.graph_temperature"))], sp)
         # projections; fx_in also feeds the to_out residual
         t1, g_fx_in = _empty(dev, N, 128), _empty(dev, N, 128)
         Wfxt, Wxt = self._T(P[f"{a}.in_project_fx.weight"]), self._T(P[f"{a}.in_project_x.weight"])
@@ -1156,19 +1133,11 @@ class Engine:
         else:
             ops.rowtile_chain(N, [Seg(g_fx_mid)], [LayerSpec(Wfxt)], [t1], res=[g_fx1])
             ops.rowtile_chain(N, [Seg(g_x_mid)], [LayerSpec(Wxt)], [g_fx_in], res=[t1])
+        group(dict(layers=[(f"{a}.in_project_x.weight", f"{a}.in_project_x.bias", 1),
+                           (f"{a}.in_project_fx.weight", f"{a}.in_project_fx.bias", 1)],
+                   tiles=[self._tile(g_x_mid, 128, Seg(fx_in)), self._tile(g_fx_mid, 128, Seg(fx_in))], M=N), [], g_x_mid, g_fx_mid, fx_in)
         if merge:
-            jobs.append(dict(layers=[(f"{a}.in_project_x.weight", f"{a}.in_project_x.bias", 1),
-                                     (f"{a}.in_project_fx.weight", f"{a}.in_project_fx.bias", 1)],
-                             tiles=[self._tile(g_x_mid, 128, Seg(fx_in)), self._tile(g_fx_mid, 128, Seg(fx_in))], M=N))
-            keep += [g_x_mid, g_fx_mid, fx_in]
-            # the block's four weight-gradient launches, then ONE reduction launch for all of their slab partials, the LayerNorm
-            # partials and the attention / slice-projection partials (11 pieces; was six reduction launches)
             self.defer(lambda: self._dw_jobs(grads, jobs, extra), *keep)
-        else:
-            self.defer(lambda: self._dw_block(grads, [(f"{a}.in_project_x.weight", f"{a}.in_project_x.bias", 1),
-                                                      (f"{a}.in_project_fx.weight", f"{a}.in_project_fx.bias", 1)],
-                                              [self._tile(g_x_mid, 128, Seg(fx_in)), self._tile(g_fx_mid, 128, Seg(fx_in))], N),
-                       g_x_mid, g_fx_mid, fx_in)
         self.flush()   # the block's parameter gradients: one fork
         return g_fx_in
 
@@ -1315,6 +1284,27 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # input preparation (importer.py:166-178)
     # ------------------------------------------------------------------------------------------------------------
+    def _normalizer_update(self, src, buffers, N, accumulate, mean_std):
+        """The Normalizer's running statistics (importer.py:123-130) take the rows of `src` [N,12] in - `accumulate` - and leave
+        mean / std in `mean_std` [18].  Data parallel: the accumulated statistics are exchanged in between."""
+        lib = L.load()
+        pws = _empty(src.device, lib.gfv_normalizer_blocks(N), 18)
+        sync = accumulate and (self.dist_world > 1 or self.dist_force)
+        if sync:
+            from . import parallel
+            before = parallel.snapshot_normalizer(buffers)
+
+        def update(acc):
+            L.check(lib.gfv_normalizer_update(src.data_ptr(), 12, N, 1 if acc else 0, buffers["acc_count"].data_ptr(),
+                                              buffers["num_accumulations"].data_ptr(), buffers["acc_sum"].data_ptr(),
+                                              buffers["acc_sum_squared"].data_ptr(), pws.data_ptr(),
+                                              mean_std.data_ptr(), L.stream_ptr()), "normalizer_update")
+        update(accumulate)
+        if sync:
+            # statistics of the GLOBAL batch on every rank, then mean / std recomputed from them (finalize only)
+            parallel.allreduce_normalizer(buffers, before, self.dist_world, self.dist_group, force=self.dist_force)
+            update(False)
+
     def prep_fwd(self, x, buffers, pl, norm_global, accumulate, want_edge_attr15=True, x_raw=None):
         """In place on x [N,12]; returns (uv_old [N,2], edge_attr16 [E,16], edge_attr15 [E,15] or None).
         Round 6: two launches - the per-graph statistics (+ the Normalizer's mean / std when it does not accumulate; + a copy of
@@ -1338,25 +1328,8 @@ class Engine:
         mean_std = _empty(dev, 18)
         fused_norm = False
         if norm_global:
-            sync = accumulate and (self.dist_world > 1 or self.dist_force)
             if accumulate:
-                nb = lib.gfv_normalizer_blocks(N)
-                pws = _empty(dev, nb, 18)
-                src = x if x_raw is None else x_raw
-                if sync:
-                    from . import parallel
-                    before = parallel.snapshot_normalizer(buffers)
-
-                def update(acc):
-                    L.check(lib.gfv_normalizer_update(src.data_ptr(), 12, N, 1 if acc else 0, buffers["acc_count"].data_ptr(),
-                                                      buffers["num_accumulations"].data_ptr(), buffers["acc_sum"].data_ptr(),
-                                                      buffers["acc_sum_squared"].data_ptr(), pws.data_ptr(),
-                                                      mean_std.data_ptr(), L.stream_ptr()), "normalizer_update")
-                update(True)
-                if sync:
-                    # statistics of the GLOBAL batch on every rank, then mean / std recomputed from them (finalize only)
-                    parallel.allreduce_normalizer(buffers, before, self.dist_world, self.dist_group, force=self.dist_force)
-                    update(False)
+                self._normalizer_update(x if x_raw is None else x_raw, buffers, N, True, mean_std)
             else:
                 fused_norm = True   # mean / std from the running buffers inside the statistics launch
         own_raw = x_raw is None
@@ -1392,23 +1365,7 @@ class Engine:
                 "norm_stats")
         mean_std = _empty(dev, 18)
         if norm_global:
-            nb = lib.gfv_normalizer_blocks(N)
-            pws = _empty(dev, nb, 18)
-            sync = accumulate and (self.dist_world > 1 or self.dist_force)
-            if sync:
-                from . import parallel
-                before = parallel.snapshot_normalizer(buffers)
-
-            def update(acc):
-                L.check(lib.gfv_normalizer_update(x.data_ptr(), 12, N, 1 if acc else 0, buffers["acc_count"].data_ptr(),
-                                                  buffers["num_accumulations"].data_ptr(), buffers["acc_sum"].data_ptr(),
-                                                  buffers["acc_sum_squared"].data_ptr(), pws.data_ptr(),
-                                                  mean_std.data_ptr(), L.stream_ptr()), "normalizer_update")
-            update(accumulate)
-            if sync:
-                # statistics of the GLOBAL batch on every rank, then mean / std recomputed from them (finalize only)
-                parallel.allreduce_normalizer(buffers, before, self.dist_world, self.dist_group, force=self.dist_force)
-                update(False)
+            self._normalizer_update(x, buffers, N, accumulate, mean_std)
         uv_old = _empty(dev, N, 2)
         L.check(lib.gfv_node_prep(x.data_ptr(), 12, pl.batch.data_ptr(), stats.data_ptr(), pl.uvp_dim.data_ptr(),
                                   mean_std.data_ptr(), 1 if norm_global else 0, uv_old.data_ptr(), N, st), "node_prep")

@@ -54,6 +54,13 @@ class RowtileArgs(C.Structure):
 ABI_VERSION = 3   # GFV_ABI_VERSION of include/gfv.h this binding is written against
 
 DW_FUSED_FLOATS = 2 * 128 * 128 + 4 * 128   # floats per workgroup block of a fused weight-gradient launch (include/gfv.h)
+# ... and where its pieces start, restating gfv_rowtile_args_t.dw_partial (include/gfv.h:200-201):
+# [dW3 (128 x 128) | db3 (128) | dW2 (128 x 128) | db2 (128) | dgamma (128) | dbeta (128)]
+DW_FUSED_WB = 128 * 128 + 128         # floats of one dW | db pair
+DW_FUSED_OFF_W3 = 0                   # dW3 | db3
+DW_FUSED_OFF_W2 = DW_FUSED_WB         # dW2 | db2
+DW_FUSED_OFF_LN = 2 * DW_FUSED_WB     # dgamma | dbeta (2 * 128 floats)
+assert DW_FUSED_OFF_LN + 256 == DW_FUSED_FLOATS
 
 
 class WimgDesc(C.Structure):

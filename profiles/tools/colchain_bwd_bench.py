@@ -73,9 +73,8 @@ for M in (75499, 603992):
         eng._dw_block(grads, [("W1c", "b1", 1)], [eng._tile(gz1, 128, Seg(e))], M)
 
     def red():
-        ops.reduce_multi([dict(partial=dwp, out=grads.view("W3"), n_chunks=nwg, chunk_stride=L.DW_FUSED_FLOATS, rows=1, cols=16384 + 128),
-                          dict(partial=dwp.data_ptr() + 4 * (16384 + 128), out=grads.view("W2"), n_chunks=nwg,
-                               chunk_stride=L.DW_FUSED_FLOATS, rows=1, cols=16384 + 128)])
+        ops.reduce_multi([eng._piece(dwp.data_ptr() + 4 * off, grads.view(w), nwg, L.DW_FUSED_FLOATS, L.DW_FUSED_WB)
+                          for off, w in ((L.DW_FUSED_OFF_W3, "W3"), (L.DW_FUSED_OFF_W2, "W2"))])
 
     chain_row()
     t = [timeit(f) for f in (chain_row, dw3, chain_col, dw1, red, chain_col1)]

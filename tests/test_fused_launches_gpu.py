@@ -229,3 +229,56 @@ def test_aggregation_from_the_saved_rows_is_bit_identical(case, family, gfv_limi
     assert len(res[True]) == len(res[False])
     for i, (a, b) in enumerate(zip(res[True], res[False])):
         assert torch.equal(a, b), (i, float((a - b).abs().max()))
+
+
+@pytest.mark.parametrize("limits", ["default", "cbwd0"])
+def test_placement_of_deferred_work_changes_no_bit(limits, gfv_limits):
+    """where the parameter-gradient work runs - queued per block and flushed on the side stream, forked at once
+    (`_defer_mode = False`), the trailing flushes on the main stream with its own slab workspace or split between the streams
+    (`_tail_main`, `_tail_split`) - decides nothing: every output and every gradient of one forward + backward equals the
+    default placement's bit for bit.  On a 4 500-cell mesh (N = 2 382 node rows, E = 6 862 edge rows: both MLP levels above
+    `_fuse_dw_min`), with the small-tile backward and - GFV_CBWD=0 - with the persistent backward that fuses the weight
+    gradients.  Named gradients are compared, never the flat buffer's alignment padding."""
+    from FVMmodel.importer import NNmodel
+    from gfv import meshgen
+    from gfv.graph import build_batch
+    from gfv.params import default_params
+    if limits == "cbwd0":
+        gfv_limits(GFV_CBWD=0)
+    nx, ny = meshgen.cylinder_grid_for_cells(4500)
+    mesh = meshgen.finish_mesh(meshgen.raw_tri_channel_cylinder(nx=nx, ny=ny, seed=5), U=0.3)
+    batch = build_batch([mesh], [meshgen.random_fields(mesh, seed=9)])
+    assert batch[0].x.shape[0] >= 2048
+    P0 = O.init_parameters(cases.WEIGHT_SEED)
+
+    def run(**attrs):
+        model = NNmodel(default_params(dataset_size=1))
+        sd = model.state_dict()
+        for k, v in P0.items():
+            sd[k].copy_(v)
+        model.load_state_dict(sd)
+        model = model.to("cuda")
+        model._replay.enabled = False
+        eng = model.engine()
+        for k, v in attrs.items():
+            assert hasattr(eng, k), k
+            setattr(eng, k, v)
+        graphs = tuple(g.clone().to("cuda") for g in batch)
+        graphs[0].norm_uvp, graphs[0].norm_global = True, True
+        o = model(*graphs)
+        torch.mean(torch.log(o[3] + 6e4 * o[0] + 5e4 * o[1] + 5e4 * o[2])).backward()
+        torch.cuda.synchronize()
+        grads = {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
+        assert len(grads) > 100
+        return [t.detach().clone() for t in o], grads
+
+    want_o, want_g = run()
+    placements = [dict(_defer_mode=False)] + [dict(_tail_env=True, _tail_main=m, _tail_split=s)
+                                              for m, s in ((1, 0), (2, 1), (2, 2), (3, 0))]
+    for attrs in placements:
+        got_o, got_g = run(**attrs)
+        assert len(got_o) == len(want_o) and got_g.keys() == want_g.keys()
+        for i, (a, b) in enumerate(zip(got_o, want_o)):
+            assert torch.equal(a, b), (attrs, i, float((a - b).abs().max()))
+        bad = [n for n in want_g if not torch.equal(got_g[n], want_g[n])]
+        assert not bad, (attrs, bad)
