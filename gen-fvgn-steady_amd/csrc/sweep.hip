@@ -1,0 +1,175 @@
+// The end of a sweep step (gfv/sweep.py: a trained model run over a device pool, slot by slot) as ONE launch - the sibling of
+// rollout_advance_kernel (csrc/rollout.hip) with per-slot state on the device, so that one recorded launch replays for every step
+// of every batch of a size signature:
+//   live slot b (slots[b].done == 0 when the launch starts):
+//     x_backup[:, 0:3] = uvp_node;  x = x_backup;  state3 = uvp_node          over the nodes of graph b
+//     age += 1;  rel = || uvp_new - uvp_prev ||_2 / || uvp_new ||_2;  streak = rel < tol ? streak + 1 : 0
+//     done = streak >= patience && age >= min_steps ? 1 : age >= max_steps ? 2 : 0
+//     last[b] = (losses[b, 0:4], || uvp_new - uvp_prev ||_2, || uvp_new ||_2)
+//   frozen slot (done != 0):  x = x_backup (x_backup is NOT overwritten);  state3 = x_backup[:, 0:3];  nothing else changes.
+// `done` is read by phase 1 as the launch finds it and written by the workgroup that arrives last, after every workgroup has
+// finished phase 1: the field a slot ends with is the prediction of the step that latched it, whatever is queued behind it.
+// Summation order as in rollout.hip: one wave per plan chunk (chunks never cross a graph), a lane sums its rows in ascending
+// order in double, a xor butterfly over the 64 lanes; the last-arriving workgroup (integer arrival counter, state[1], left at
+// zero) folds the chunks of each graph - lane l takes chunks l, l + 64, ... - and butterflies again.  No floating-point atomics.
+#include "../../include/gfv.h"
+#include "gfv_common.h"
+#include "gfv_launch.h"
+#include "gfv_prof.h"
+
+namespace {
+
+constexpr int SW_WAVES = 4;
+
+struct SweepCtl {
+  float tol;                  // negative: never converge
+  int min_steps, max_steps, patience;
+};
+
+struct SweepArgs {
+  const float* uvp_node;      // [N,3]
+  float* x_backup;            // [N,12]
+  float* x;                   // [N,12]
+  const int* chunk_beg;       // [n_chunks]
+  const int* chunk_end;
+  const int* gchunk_ptr;      // [B+1]
+  const float* losses;        // [B,4]
+  double* partial;            // [n_chunks,2]
+  const SweepCtl* ctl;
+  int* slots;                 // [B,4]: age, streak, done, reserved
+  float* last;                // [B,6]
+  float* state3;              // [N,3]
+  int* mirror;                // pinned, device-mapped: [0] step sequence number, [1 + 2b] done, [2 + 2b] age
+  int* state;                 // [2]: step sequence number, arrival counter
+  int N, n_chunks, B;
+};
+
+__device__ __forceinline__ double sw_wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64 * SW_WAVES) void sweep_advance_kernel(const SweepArgs A) {
+  __shared__ int s_last;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int c = blockIdx.x * SW_WAVES + wave;
+  if (c < A.n_chunks) {
+    int b = 0;   // the chunk's graph
+    while (b < A.B - 1 && A.gchunk_ptr[b + 1] <= c) ++b;
+    const bool live = A.slots[4 * b + 2] == 0;
+    const int beg = A.chunk_beg[c], end = min(A.chunk_end[c], A.N);
+    double d2 = 0.0, n2 = 0.0;
+    for (int i = beg + lane; i < end; i += 64) {
+      if (i < 0) continue;
+      float4* xb = reinterpret_cast<float4*>(A.x_backup + (size_t)i * 12);
+      float4* xo = reinterpret_cast<float4*>(A.x + (size_t)i * 12);
+      float* s3 = A.state3 + (size_t)i * 3;
+      float4 r0 = xb[0];
+      const float4 r1 = xb[1], r2 = xb[2];
+      if (live) {
+        const float* u = A.uvp_node + (size_t)i * 3;
+        const float u0 = u[0], u1 = u[1], u2 = u[2];
+        const float e0 = u0 - r0.x, e1 = u1 - r0.y, e2 = u2 - r0.z;
+        d2 += ((double)e0 * (double)e0 + (double)e1 * (double)e1) + (double)e2 * (double)e2;
+        n2 += ((double)u0 * (double)u0 + (double)u1 * (double)u1) + (double)u2 * (double)u2;
+        r0.x = u0; r0.y = u1; r0.z = u2;
+        xb[0] = r0;
+      }
+      xo[0] = r0; xo[1] = r1; xo[2] = r2;
+      s3[0] = r0.x; s3[1] = r0.y; s3[2] = r0.z;
+    }
+    d2 = sw_wave_sum(d2);
+    n2 = sw_wave_sum(n2);
+    if (lane == 0) {
+      A.partial[2 * (size_t)c] = d2;
+      A.partial[2 * (size_t)c + 1] = n2;
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  if (tid == 0) s_last = atomicAdd(A.state + 1, 1) == (int)gridDim.x - 1;
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  const float tol = A.ctl->tol;
+  const int min_steps = A.ctl->min_steps, max_steps = A.ctl->max_steps, patience = A.ctl->patience;
+  for (int b = wave; b < A.B; b += SW_WAVES) {
+    int* s = A.slots + 4 * b;
+    int age = s[0], streak = s[1], done = s[2];
+    if (done == 0) {
+      const int c0 = A.gchunk_ptr[b], c1 = min(A.gchunk_ptr[b + 1], A.n_chunks);
+      double d2 = 0.0, n2 = 0.0;
+      for (int q = c0 + lane; q < c1; q += 64) {
+        d2 += __hip_atomic_load(A.partial + 2 * (size_t)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        n2 += __hip_atomic_load(A.partial + 2 * (size_t)q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      d2 = sw_wave_sum(d2);
+      n2 = sw_wave_sum(n2);
+      const float dn = (float)sqrt(d2), un = (float)sqrt(n2);
+      const float rel = dn / un;                 // (0 / 0 and x / 0: NaN and inf compare false)
+      age += 1;
+      streak = rel < tol ? streak + 1 : 0;
+      if (streak >= patience && age >= min_steps) done = 1;
+      else if (age >= max_steps) done = 2;
+      float* h = A.last + 6 * (size_t)b;
+      if (lane < 4) h[lane] = A.losses[4 * b + lane];
+      if (lane == 4) h[4] = dn;
+      if (lane == 5) h[5] = un;
+      if (lane == 0) { s[0] = age; s[1] = streak; s[2] = done; }
+    }
+    if (lane == 0) {
+      __hip_atomic_store(A.mirror + 1 + 2 * b, done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(A.mirror + 2 + 2 * b, age, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  __threadfence_system();
+  __syncthreads();
+  // (per-lane vector stores of the two counters)
+  if (tid == 0) {
+    const int seq = A.state[0] + 1;
+    A.state[0] = seq;
+    A.state[1] = 0;
+    __hip_atomic_store(A.mirror, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+
+}  // namespace
+
+extern "C" int gfv_sweep_mirror_create(int32_t n_words, int32_t** host_words, int32_t** dev_words) {
+  if (n_words <= 0 || !host_words || !dev_words) return GFV_ERR_ARG;
+  void* h = nullptr;
+  void* d = nullptr;
+  if (hipHostMalloc(&h, sizeof(int32_t) * (size_t)n_words, hipHostMallocMapped) != hipSuccess) return GFV_ERR_LAUNCH;
+  for (int32_t i = 0; i < n_words; ++i) static_cast<int32_t*>(h)[i] = 0;
+  if (hipHostGetDevicePointer(&d, h, 0) != hipSuccess) {
+    (void)hipHostFree(h);
+    return GFV_ERR_LAUNCH;
+  }
+  *host_words = static_cast<int32_t*>(h);
+  *dev_words = static_cast<int32_t*>(d);
+  return GFV_OK;
+}
+
+extern "C" int gfv_sweep_mirror_free(int32_t* host_words) {
+  if (!host_words) return GFV_ERR_ARG;
+  return hipHostFree(host_words) == hipSuccess ? GFV_OK : GFV_ERR_LAUNCH;
+}
+
+extern "C" int gfv_sweep_advance(const float* uvp_node, float* x_backup, float* x, int32_t N, const int32_t* chunk_beg,
+                                 const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B,
+                                 const float* losses, double* partial_ws, const void* ctl, int32_t* slots, float* last,
+                                 float* state3, int32_t* mirror_dev, int32_t* state, void* stream) {
+  if (!uvp_node || !x_backup || !x || !chunk_beg || !chunk_end || !gchunk_ptr || !losses || !partial_ws || !ctl || !slots ||
+      !last || !state3 || !mirror_dev || !state)
+    return GFV_ERR_ARG;
+  if (N <= 0 || n_chunks <= 0 || B <= 0) return GFV_ERR_ARG;
+  if ((reinterpret_cast<size_t>(x_backup) | reinterpret_cast<size_t>(x)) & 15) return GFV_ERR_ARG;
+  // rows: uvp [N,3] read, x_backup [N,12] read, 16 B of it, x [N,12] and state3 [N,3] written
+  GfvProfScope ps_(GFV_K_MISC, 0, (12.0 + 48.0 + 16.0 + 48.0 + 12.0) * N, stream);
+  const SweepArgs a{uvp_node, x_backup, x, chunk_beg, chunk_end, gchunk_ptr, losses, partial_ws,
+                    static_cast<const SweepCtl*>(ctl), slots, last, state3, mirror_dev, state, N, n_chunks, B};
+  GFV_LAUNCH(sweep_advance_kernel, dim3((n_chunks + SW_WAVES - 1) / SW_WAVES), dim3(64 * SW_WAVES), 0, (hipStream_t)stream, a);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}

@@ -39,7 +39,8 @@ _QUERIES = frozenset((
     "gfv_profile_collect", "gfv_profile_reset", "gfv_profile_set_sizes", "gfv_status_flags", "gfv_status_mirror", "gfv_prep_workspace_bytes", "gfv_get_limit", "gfv_set_limit", "gfv_limit_name", "gfv_rowtile_dw_partials", "gfv_rowtile_dw_partials_m",
     "gfv_rowtile_fuses_dw", "gfv_graph_norm_workspace_bytes", "gfv_plan_create", "gfv_plan_destroy", "gfv_plan_table", "gfv_plan_sizes",
     "gfv_record_begin", "gfv_record_count", "gfv_record_end", "gfv_record_length", "gfv_record_replay", "gfv_record_free",
-    "gfv_record_delay_side", "gfv_pool_args_bytes", "gfv_pool_table_bytes", "gfv_pool_table_check"))
+    "gfv_record_delay_side", "gfv_pool_args_bytes", "gfv_pool_table_bytes", "gfv_pool_table_check",
+    "gfv_sweep_mirror_create", "gfv_sweep_mirror_free"))
 
 
 class CommandList:

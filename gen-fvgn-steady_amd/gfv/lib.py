@@ -241,6 +241,11 @@ _SIGNATURES = {
     "gfv_plan_sizes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "gfv_rollout_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gfv_sweep_mirror_create": (C.c_int, [C.c_int32, C.POINTER(C.POINTER(C.c_int32)), C.POINTER(C.c_void_p)]),
+    "gfv_sweep_mirror_free": (C.c_int, [C.POINTER(C.c_int32)]),
+    "gfv_sweep_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_void_p]),
     "gfv_trans_mlp_fwd": (C.c_int, [C.POINTER(TransMlp), C.c_void_p]),
     "gfv_trans_mlp_bwd": (C.c_int, [C.POINTER(TransMlpBwd), C.c_void_p]),
     "gfv_trans_mlp_ln_rows": (C.c_int, [C.c_int32]),

@@ -1,0 +1,362 @@
+"""Sweep: run a trained model over the entries of a device pool, slot by slot (continuous batching of a parameter sweep).
+
+The reference solves one case at a time (`solve_without_grad_GPU.py:117-173`); `gfv.rollout.Rollout` is that loop for ONE batch,
+bound to the graphs it was built with, and its `run(tol=...)` stops a batch only when its slowest member is below the tolerance.
+`Sweep` is the inference twin of `gfv.pool_trainer.PoolTrainStep`: a fixed number of slots in a `BatchArena`, every slot advances
+its own pool entry until THAT entry meets the criterion and is frozen on the device at that step; a retired slot takes the next
+pending entry.
+
+    sw = Sweep(model, pool, max_graphs=8, tol=1e-6, max_steps=40000)
+    results = sw.run()                  # results[i]: entry, steps, converged, losses (4 floats), rel_update
+    sw.stats()                          # {"steps", "swaps", "replayed", "recorded", "eager", "lists", "list_bytes"}
+
+The fields themselves are in the pool afterwards (entry `x[:, 0:3]`), as after `PoolTrainStep.step(payback=True)`.
+
+The step is `Rollout._body` over the arena's plan and `x` / `x_raw` - the forward-only engine path on static weight images - with
+`gfv_sweep_advance` (csrc/sweep.hip) in place of `gfv_rollout_advance`: per-slot `age / streak / done` live on the device, the
+criterion is evaluated there, and a slot whose `done` is set keeps its state whatever is queued behind it.  That is what lets the
+host run ahead without synchronising (`max_ahead`) and makes an entry's result independent of its neighbours.
+
+Recorded lists are kept per ordered batch signature (variants of one mesh share it: one list serves the whole sweep): two eager
+warm-up steps, then record, then replay; bounded by `max_list_bytes`, least recently used out.
+
+Who owns what a recorded list points at.  (1) The list's private memory pool: activations and outputs.  (2) The arena: the plan,
+`x`, `x_raw`.  (3) This object, for its lifetime, never reallocated: `ctl`, `slots`, `last`, `state3`, the reduction workspace,
+the counters, the pinned mirror, the padded parameters of a narrow model and the engine scratch of the input preparation and of
+the finite-volume tail, sized for `max_graphs` and swapped into the engine for the duration of a step (`Rollout._own_scratch`'s
+rule).  (4) The engine's static weight-image set (checked against `WeightGuard` and the engine signature before a run).
+
+A swap (the mirror shows a retired slot and something is pending): synchronise; read `slots` / `last` from device memory; pay
+`state3` back into ALL current entries; record the retired entries' results; load the new index list; zero the swapped slots.
+The mirror is only a hint that a synchronisation is worth it - every value acted on is read from device memory after it.
+"""
+from __future__ import annotations
+
+import collections
+import contextlib
+import ctypes as C
+import math
+import struct
+
+import torch
+
+from . import cmdlist
+from . import lib as L
+from .functions import require_gpu
+from .rollout import WeightGuard
+
+SweepResult = collections.namedtuple("SweepResult", "entry steps converged losses rel_update")
+
+DONE_LIVE, DONE_CONVERGED, DONE_MAX_STEPS = 0, 1, 2
+
+
+# ---- host-side checks and the scheduler: no GPU ------------------------------------------------------------------------------
+def check_max_steps(max_steps):
+    """Termination is enforced on the device by `max_steps`: it has to be a finite positive whole number."""
+    try:
+        ok = math.isfinite(max_steps) and max_steps >= 1 and int(max_steps) == max_steps and max_steps < 2 ** 31
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"Sweep: max_steps must be a finite positive integer, not {max_steps!r} (it is what ends a slot that "
+                         "never converges)")
+    return int(max_steps)
+
+
+def check_entries(entries, n):
+    """-> the entries as a list of ints; ValueError for a duplicate or an entry outside the pool of `n`."""
+    out = list(range(n)) if entries is None else [int(e) for e in entries]
+    for e in out:
+        if not 0 <= e < n:
+            raise ValueError(f"Sweep: pool entry {e} does not exist (the pool holds {n})")
+    if len(set(out)) != len(out):
+        raise ValueError("Sweep: an entry appears more than once (each entry is solved once and written back once)")
+    return out
+
+
+class SlotScheduler:
+    """Which entry runs in which slot.  Slots are filled from the pending queue in order; a retired slot takes the first pending
+    entry with the SAME entry signature (the batch signature - and with it the recorded list - stays), else the first pending
+    entry of any signature; with nothing pending it keeps its (frozen) entry.  A live entry never changes slot."""
+
+    def __init__(self, entries, signature_of, n_slots):
+        if int(n_slots) < 1:
+            raise ValueError("a sweep needs at least one slot")
+        self.pending = collections.deque(entries)
+        self.sig = {e: signature_of(e) for e in entries}
+        self.n_slots = int(n_slots)
+        self.slots = []
+
+    def start(self):
+        """-> the entries of the first batch, slot by slot."""
+        while self.pending and len(self.slots) < self.n_slots:
+            self.slots.append(self.pending.popleft())
+        return list(self.slots)
+
+    def replace(self, retired):
+        """`retired`: slot numbers whose entries are finished -> {slot: new entry} for those that got one."""
+        new = {}
+        for b in sorted(retired):
+            if not self.pending:
+                break
+            want = self.sig[self.slots[b]]
+            pick = next((e for e in self.pending if self.sig[e] == want), self.pending[0])
+            self.pending.remove(pick)
+            self.slots[b] = pick
+            new[b] = pick
+        return new
+
+    def batch_signature(self):
+        return tuple(self.sig[e] for e in self.slots)
+
+
+class _Recorded:
+    __slots__ = ("cl", "bytes")
+
+    def __init__(self, cl, nbytes):
+        self.cl, self.bytes = cl, nbytes
+
+
+class Sweep:
+    WARM = 2        # eager steps of a batch signature before its list is recorded (they are steps of the sweep like any other)
+    EVICT_MAX = 2   # a signature that lost its list to the byte budget this often stays eager (PoolTrainStep's rule)
+
+    def __init__(self, model, pool, max_graphs=8, tol=1e-6, max_steps=40000, min_steps=1, patience=1, max_ahead=64,
+                 launch_mode="cmd_list", max_list_bytes=16 << 30, max_sizes=None):
+        if launch_mode not in ("cmd_list", "eager"):
+            raise ValueError('launch_mode must be "cmd_list" or "eager"')
+        self.max_steps = check_max_steps(max_steps)
+        if int(min_steps) < 0 or int(patience) < 1 or int(max_ahead) < 0:
+            raise ValueError("Sweep: min_steps >= 0, patience >= 1 and max_ahead >= 0 are required")
+        self.tol, self.min_steps, self.patience = float(tol), int(min_steps), int(patience)
+        if math.isnan(self.tol):
+            raise ValueError("Sweep: tol is NaN (a negative tol means: never converge)")
+        self.max_ahead = int(max_ahead)
+        self.launch_mode, self.max_list_bytes = launch_mode, int(max_list_bytes)
+        self.model, self.pool = model, pool
+        self._check_normalizer()
+        require_gpu(pool.x[0])
+        self.arena = pool.arena(max_graphs, max_sizes)
+        self.engine = model.engine()
+        dev = self.dev = pool.device
+        cap, B = self.arena.capacity, self.arena.max_graphs
+        self.norm_global = True        # (what the graphs of a pool carry: gfv.pool.BatchArena._make_views)
+        lib = L.load()
+        # device-resident state of the slots and what the advance launch works on: created once, never reallocated
+        self._ctl = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._slots = torch.zeros((B, 4), dtype=torch.int32, device=dev)
+        self._last = torch.zeros((B, 6), dtype=torch.float32, device=dev)
+        self._state3 = torch.zeros((max(cap["n"], 1), 3), dtype=torch.float32, device=dev)
+        self._partial = torch.zeros((max(cap["nchunk"], 1), 2), dtype=torch.float64, device=dev)
+        self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # (step sequence number, arrival counter)
+        self._prep_ws = torch.zeros(max(lib.gfv_prep_workspace_bytes(B) // 4, 1), dtype=torch.float32, device=dev)
+        self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)
+        self._mirror_words = 1 + 2 * B
+        host, devp = C.POINTER(C.c_int32)(), C.c_void_p()
+        L.check(L.load(raw=True).gfv_sweep_mirror_create(self._mirror_words, C.byref(host), C.byref(devp)), "gfv_sweep_mirror_create")
+        self._mirror, self._mirror_dev = host, devp.value
+        L.status_mirror()
+        self._lists = collections.OrderedDict()      # batch signature -> _Recorded, least recently used first
+        self._warm, self._oversize, self._evicted = {}, set(), {}
+        self._counts = dict(steps=0, swaps=0, replayed=0, recorded=0, eager=0)
+        self._guard = WeightGuard(model)
+        self.refresh_weights()
+
+    def __del__(self):
+        host = getattr(self, "_mirror", None)
+        if host:
+            try:
+                self._lists.clear()
+                torch.cuda.synchronize(self.dev)     # (nothing queued may still publish into the mirror)
+                L.load(raw=True).gfv_sweep_mirror_free(host)
+            except Exception:
+                pass
+            self._mirror = None
+
+    # ---- guards --------------------------------------------------------------------------------------------------------
+    def _check_normalizer(self):
+        if self.model.node_norm.should_accumulate():
+            raise ValueError("Sweep: the model's Normalizer is still accumulating; its statistics would couple the graphs of a "
+                             "batch, so an entry's result would depend on its neighbours.  Sweep a trained model")
+
+    def refresh_weights(self):
+        """(Re)build what depends on the parameter VALUES: padded copies (hidden_size < 128) and the forward weight images.
+        Recorded lists are dropped (the next steps warm up and record again)."""
+        from FVMmodel.padding import pad_parameters
+        names, tensors = self.model.param_names_tensors()
+        with torch.no_grad():
+            padded = pad_parameters(names, tensors, self.model.hidden_size)
+            self.P = dict(zip(names, (t.detach() for t in padded)))
+        self.buffers = self.model.node_norm.buffers_dict()
+        self.model.node_norm._host_num_acc = None
+        self._lists.clear()
+        self._warm = {}
+        with self.engine.model_width():
+            self.engine.build_static_images(self.P)
+        self._guard.refresh()
+        self._sig = self._engine_signature()
+
+    def _engine_signature(self):
+        """As Rollout._engine_signature: parameter set, product form, identity of the image set."""
+        sig = self.engine.capture_signature()
+        wi = self.engine._wi
+        return (sig[0], sig[2], None if wi is None else id(wi["fwd"]))
+
+    def stats(self):
+        return dict(self._counts, lists=len(self._lists), list_bytes=sum(e.bytes for e in self._lists.values()))
+
+    # ---- one step ------------------------------------------------------------------------------------------------------
+    @contextlib.contextmanager
+    def _own_scratch(self):
+        eng = self.engine
+        saved = (eng._prep_ws, eng._fvm_cnt)
+        eng._prep_ws, eng._fvm_cnt = self._prep_ws, self._fvm_cnt
+        try:
+            yield
+        finally:
+            assert eng._prep_ws is self._prep_ws and eng._fvm_cnt is self._fvm_cnt, "engine scratch was reallocated inside a step"
+            eng._prep_ws, eng._fvm_cnt = saved
+
+    def _body(self, graphs, pl):
+        x, x_raw = graphs[0].x, graphs[0]._gfv_x_raw
+        with self._own_scratch(), self.engine.model_width():
+            losses, uvp_node, _, _, sv = self.engine.forward(
+                self.P, self.buffers, x, pl, norm_global=self.norm_global, accumulate=False, want_outputs=True,
+                want_edge_attr15=False, x_raw=x_raw, keep=False, static_weights=True)
+        assert sv is None
+        L.check(L.load().gfv_sweep_advance(
+            uvp_node.data_ptr(), x_raw.data_ptr(), x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(), pl.chunk_end.data_ptr(),
+            pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(), self._ctl.data_ptr(),
+            self._slots.data_ptr(), self._last.data_ptr(), self._state3.data_ptr(), self._mirror_dev, self._state.data_ptr(),
+            L.stream_ptr()), "gfv_sweep_advance")
+        L.status_publish()
+        return losses, uvp_node
+
+    def _step(self, key, graphs, pl):
+        self._counts["steps"] += 1
+        listed = self.launch_mode == "cmd_list" and self.max_list_bytes > 0 and key not in self._oversize
+        ent = self._lists.get(key) if listed else None
+        if ent is not None:
+            self._lists.move_to_end(key)
+            ent.cl.replay()
+            self._counts["replayed"] += 1
+        elif not listed or self._warm.get(key, 0) < Sweep.WARM:
+            if listed:
+                self._warm[key] = self._warm.get(key, 0) + 1
+            self._body(graphs, pl)
+            self._counts["eager"] += 1
+        else:
+            before = torch.cuda.memory_reserved(self.dev)
+            with cmdlist.record() as cl:
+                cl.keep.append(self._body(graphs, pl))
+            nbytes = max(torch.cuda.memory_reserved(self.dev) - before, 0)      # the segments of the list's private pool
+            self._counts["recorded"] += 1
+            if nbytes > self.max_list_bytes:
+                self._oversize.add(key)
+                return
+            self._lists[key] = _Recorded(cl, nbytes)
+            while sum(e.bytes for e in self._lists.values()) > self.max_list_bytes and len(self._lists) > 1:
+                old, _ = self._lists.popitem(last=False)
+                self._evicted[old] = self._evicted.get(old, 0) + 1
+                if self._evicted[old] >= Sweep.EVICT_MAX:
+                    self._oversize.add(old)
+
+    # ---- the run -------------------------------------------------------------------------------------------------------
+    def _write_ctl(self):
+        words = struct.unpack("4i", struct.pack("f3i", self.tol, self.min_steps, self.max_steps, self.patience))
+        self._ctl.copy_(torch.tensor(words, dtype=torch.int32))
+
+    def _read_slots(self):
+        """(synchronises) -> slots [B,4] and last [B,6] as the device holds them."""
+        torch.cuda.current_stream().synchronize()
+        return self._slots.cpu(), self._last.cpu()
+
+    @staticmethod
+    def _result(entry, slot_row, last_row):
+        d, n = float(last_row[4]), float(last_row[5])
+        rel = d / n if n != 0.0 else float("nan")
+        return SweepResult(entry, int(slot_row[0]), int(slot_row[2]) == DONE_CONVERGED, tuple(float(v) for v in last_row[0:4]), rel)
+
+    def run(self, entries=None):
+        """Solve the pool entries `entries` (None: all of them) -> a list of SweepResult in the order of `entries`; the fields are
+        written back into the pool entries' `x[:, 0:3]`."""
+        L.raise_on_status("Sweep.run")
+        ents = check_entries(entries, self.pool.n)
+        self._check_normalizer()
+        self._guard.check()
+        if self._engine_signature() != self._sig:
+            raise RuntimeError("Sweep: the engine's weight-image set changed under the sweep (another parameter set or product "
+                               "form went through the same engine); call refresh_weights()")
+        if not ents:
+            return []
+        sched = SlotScheduler(ents, lambda e: self.arena.signature([e])[0], self.arena.max_graphs)
+        cur = sched.start()
+        B = len(cur)
+        stream = torch.cuda.current_stream()
+        stream.synchronize()
+        for i in range(self._mirror_words):
+            self._mirror[i] = 0
+        self._write_ctl()
+        self._slots.zero_()
+        self._last.zero_()
+        self._state.zero_()
+        graphs, pl = self.arena.load(cur)
+        key = sched.batch_signature()
+        state3 = self._state3[:pl.N]
+        results, harvested = {}, set()        # entry -> SweepResult; slots whose current entry's result has been recorded
+        issued = known = 0                    # steps issued since the counters were zeroed; of those, known to have completed
+        taken = [0] * B                       # steps issued since the slot was loaded: at max_steps it is done, mirror or not
+        events = collections.deque()
+        while True:
+            self._step(key, graphs, pl)
+            issued += 1
+            taken = [t + 1 for t in taken]
+            if self.max_ahead == 0:
+                stream.synchronize()
+                known = issued
+            else:
+                if issued % self.max_ahead == 0:
+                    ev = torch.cuda.Event()
+                    ev.record(stream)
+                    events.append((issued, ev))
+                known = max(known, min(int(self._mirror[0]), issued))
+                while issued - known >= self.max_ahead and events:
+                    n, ev = events.popleft()
+                    ev.synchronize()
+                    known = max(known, n)
+            # the mirror: a hint that a synchronisation is worth it (a slot that has been issued max_steps steps needs none)
+            retired = [b for b in range(B) if b not in harvested
+                       and (self._mirror[1 + 2 * b] != DONE_LIVE or taken[b] >= self.max_steps)]
+            if not retired:
+                continue
+            if not sched.pending and len(retired) + len(harvested) < B:
+                continue                      # (nothing to hand out, and live slots remain: keep going)
+            slots, last = self._read_slots()  # (synchronises: from here on, what the device holds)
+            events.clear()
+            known = issued
+            done = [b for b in range(B) if int(slots[b, 2]) != DONE_LIVE]
+            self.arena.payback(cur, state3)
+            for b in done:
+                if b not in harvested:
+                    results[cur[b]] = self._result(cur[b], slots[b], last[b])
+                    harvested.add(b)
+            new = sched.replace(done)
+            if not new:
+                if len(harvested) == B:
+                    break                     # every slot done, nothing pending: the payback above was the final one
+                continue
+            self._counts["swaps"] += 1
+            cur = list(sched.slots)
+            graphs, pl = self.arena.load(cur)
+            key = sched.batch_signature()
+            state3 = self._state3[:pl.N]
+            for b in new:
+                self._slots[b].zero_()
+                self._mirror[1 + 2 * b] = 0
+                self._mirror[2 + 2 * b] = 0
+                harvested.discard(b)
+                taken[b] = 0
+        stream.synchronize()
+        L.raise_on_status("Sweep.run")
+        self._current = (key, graphs, pl)     # (what the arena holds: every slot frozen)
+        return [results[e] for e in ents]

@@ -805,6 +805,39 @@ int gfv_rollout_advance(const float* uvp_node, float* x_backup, float* x, int32_
                         double* partial_ws, float* history, int32_t K_max, int32_t* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Sweep (gfv/sweep.py: a trained model run over the entries of a device pool, slot by slot).  The end of a sweep step as ONE
+ * launch: gfv_rollout_advance with per-slot state on the device, so that one recorded launch replays for every step of every
+ * batch.  Beside what gfv_rollout_advance takes (no history: per-step records are gfv.rollout.Rollout's):
+ *   ctl        16 bytes of device memory the host writes between steps: {float tol (negative: never converge), int32 min_steps,
+ *              max_steps, patience}
+ *   slots      [B, 4] int32: age (steps this entry has taken), streak (consecutive steps with a relative update below tol),
+ *              done (0 live, 1 converged, 2 stopped at max_steps), reserved
+ *   last       [B, 6] float: the gfv_rollout_advance history row of the slot's last live step
+ *   state3     [N, 3] float: what x_backup[:, 0:3] holds after the launch, compact (the source of gfv_pool_payback)
+ *   mirror_dev the device address of a pinned, device-mapped int32 array of at least 1 + 2 B words (gfv_sweep_mirror_create):
+ *              [0] the step sequence number, [1 + 2 b] done and [2 + 2 b] age of slot b - a hint the host reads without a
+ *              synchronisation; whatever it acts on it reads from slots / last after one
+ *   state      two int32 (step sequence number, arrival counter), the second zero before the first launch and left zero
+ * For slot b = the graph of a chunk (gchunk_ptr), with done[b] AS THE LAUNCH FINDS IT:
+ *   live:    x_backup[:, 0:3] = uvp_node; x = x_backup; state3 = uvp_node; then, by the workgroup that arrives last:
+ *            age += 1; rel = || uvp_node - uvp_prev ||_2 / || uvp_node ||_2 (fp32 quotient of the two fp32 norms);
+ *            streak = rel < tol ? streak + 1 : 0 (a NaN or a zero norm compares false);
+ *            done = 1 if streak >= patience && age >= min_steps, else 2 if age >= max_steps; last[b] is written
+ *   frozen:  x = x_backup; state3 = x_backup[:, 0:3]; x_backup, slots[b] and last[b] stay as they are
+ * done is written only after every workgroup has arrived: a slot's final field is the prediction of the step that latched it,
+ * whatever was queued behind it.  Sums in the fixed order of gfv_rollout_advance; no floating-point atomics.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, a size < 1 or an x_backup / x that is not 16-byte aligned.
+ * gfv_sweep_mirror_create: n_words zeroed int32 of pinned, device-mapped host memory -> its host and device addresses;
+ * gfv_sweep_mirror_free takes the host address.  GFV_ERR_ARG on n_words < 1 or a NULL pointer.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gfv_sweep_mirror_create(int32_t n_words, int32_t** host_words, int32_t** dev_words);
+int gfv_sweep_mirror_free(int32_t* host_words);
+int gfv_sweep_advance(const float* uvp_node, float* x_backup, float* x, int32_t N, const int32_t* chunk_beg,
+                      const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* losses,
+                      double* partial_ws, const void* ctl, int32_t* slots, float* last, float* state3, int32_t* mirror_dev,
+                      int32_t* state, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Pool training (gfv/pool.py BatchArena, gfv/pool_trainer.py; the changing-batch loop of pre_train_Adam.py:112-198 with
  * Data_Pool.payback, Graph_loader.py:370-396): a batch of ANY entries of the device-resident pool assembled into FIXED memory
  * by one launch, and the prediction written back by one launch.
