@@ -389,21 +389,38 @@ __global__ void adam_state_init_kernel(float* state, float t_done, double b1, do
   adam_corrections(state, pow(b1, tn), pow(b2, tn));
 }
 
+// guard[8] (include/gfv.h): what gfv_grad_guard_dev decides for the Adam launch behind it
+enum { GD_MAX_NORM = 0, GD_POLICY = 1, GD_NORM = 2, GD_COEF = 3, GD_DECISION = 4, GD_N_CLIPPED = 5, GD_N_NONFINITE = 6,
+       GD_N_FLAG = 7 };
+
 constexpr int ADAM_TPB = 512, ADAM_MAX_WGS = 512;   // (few workgroups: one same-address atomic each at the end)
+// GUARDED: the step of gfv_adam_step_guarded_dev - the gradient times the clip coefficient of guard[], or no step at all.
+// The plain form (GUARDED = false, guard unused) is the kernel it has always been.
+template <bool GUARDED>
 __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n, float* state,
-                                                        const float* __restrict__ hyper, const int* status_dev, int* status_host) {
+                                                        const float* __restrict__ hyper, const int* status_dev, int* status_host,
+                                                        const float* __restrict__ guard) {
   const float step_size = (float)((double)hyper[0] / as_get(state, AS_BC1_HI)), bc2_sqrt = state[AS_SQRT_BC2];
   const float t_done = state[AS_T];
   const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], grad_scale = hyper[4];
   const float omb1 = state[AS_OMB1], omb2 = state[AS_OMB2];
-  for (long i = (long)blockIdx.x * ADAM_TPB + threadIdx.x; i < n; i += (long)gridDim.x * ADAM_TPB) {
-    const float gi = g[i] * grad_scale;
-    const float mi = m[i] * b1 + omb1 * gi;
-    const float vi = v[i] * b2 + omb2 * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] - step_size * (mi / denom);
+  float coef = 1.0f;
+  bool skip = false;
+  if constexpr (GUARDED) {
+    coef = guard[GD_COEF];
+    skip = (reinterpret_cast<const int*>(guard)[GD_DECISION] & (GFV_GUARD_SKIP_NONFINITE | GFV_GUARD_SKIP_FLAG)) != 0;
+  }
+  if (!skip) {
+    for (long i = (long)blockIdx.x * ADAM_TPB + threadIdx.x; i < n; i += (long)gridDim.x * ADAM_TPB) {
+      float gi = g[i] * grad_scale;
+      if constexpr (GUARDED) gi = gi * coef;
+      const float mi = m[i] * b1 + omb1 * gi;
+      const float vi = v[i] * b2 + omb2 * gi * gi;
+      m[i] = mi; v[i] = vi;
+      const float denom = sqrtf(vi) / bc2_sqrt + eps;
+      p[i] = p[i] - step_size * (mi / denom);
+    }
   }
   __syncthreads();   // every thread of this workgroup has read the state (the values were consumed by the loop above)
   if (threadIdx.x == 0) {
@@ -413,14 +430,96 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
     // first form of this kernel took 115 us instead of 8.)
     if (__hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
       *counter = 0;
-      state[AS_T] = t_done + 1.0f;
-      adam_corrections(state, as_get(state, AS_P1) * as_get(state, AS_B1), as_get(state, AS_P2) * as_get(state, AS_B2));
+      if (!skip) {   // (a skipped step is no step: t and the running powers stay)
+        state[AS_T] = t_done + 1.0f;
+        adam_corrections(state, as_get(state, AS_P1) * as_get(state, AS_B1), as_get(state, AS_P2) * as_get(state, AS_B2));
+      }
       if (status_host) {
         const int f = *reinterpret_cast<const volatile int*>(status_dev);
         if (f) __hip_atomic_store(status_host, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       }
     }
   }
+}
+
+// Global L2 norm of the scaled gradient over a table of (offset, count) segments of the flat buffer, and the decision the
+// guarded Adam launch reads (include/gfv.h gfv_grad_guard_dev).  Every segment is cut into tiles of GUARD_TILE elements; tile t
+// of segment s belongs to workgroup (s + t) % gridDim.x (the many one-tile segments of a model - biases, LayerNorm vectors -
+// spread over the grid instead of piling up on workgroup 0).  Nothing outside a segment is read.  Sums are double and every
+// order is fixed: a thread adds its elements in tile order, the lanes of a wave fold by xor butterflies, the four waves in
+// order, and the workgroup that arrives last adds the per-workgroup partials in index order - same inputs, same bits.
+// The hand-off of the partials carries no fence, for the reason written above adam_kernel (the backward has just dirtied the
+// L2 with the gradient): thread 0 stores its workgroup's partial write-through (an agent-scope atomic store), waits for that
+// store, then adds to the arrival counter; the last arriver reads the partials with agent-scope loads that bypass its L1.
+constexpr int GUARD_TPB = 256, GUARD_PER_THREAD = 4, GUARD_TILE = GUARD_TPB * GUARD_PER_THREAD, GUARD_MAX_WGS = 256;
+__global__ __launch_bounds__(GUARD_TPB) void grad_guard_kernel(const float* __restrict__ g, const long* __restrict__ segs, int n_seg,
+                                                               const float* __restrict__ hyper, float* guard, double* partials,
+                                                               int* counter, const int* status_dev) {
+  __shared__ double red[GUARD_TPB / 64];
+  __shared__ double fold[GUARD_MAX_WGS];
+  __shared__ int last;
+  const int tid = threadIdx.x, blk = blockIdx.x, nblk = gridDim.x;
+  const float grad_scale = hyper[4];
+  double acc = 0.0;
+  for (int s = 0; s < n_seg; ++s) {
+    const long off = segs[2 * s], cnt = segs[2 * s + 1];
+    const long tiles = (cnt + GUARD_TILE - 1) / GUARD_TILE;
+    long t = (long)(blk - s % nblk);
+    if (t < 0) t += nblk;
+    for (; t < tiles; t += nblk) {
+      const long base = t * GUARD_TILE + tid;
+      float x[GUARD_PER_THREAD];
+#pragma unroll
+      for (int u = 0; u < GUARD_PER_THREAD; ++u) {
+        const long i = base + (long)u * GUARD_TPB;
+        x[u] = i < cnt ? g[off + i] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < GUARD_PER_THREAD; ++u) {
+        const double d = (double)(x[u] * grad_scale);
+        acc += d * d;
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((tid & 63) == 0) red[tid >> 6] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    const double part = (red[0] + red[1]) + (red[2] + red[3]);
+    __hip_atomic_store(partials + blk, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the partial has left this CU before the counter says so
+    last = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  for (int i = tid; i < nblk; i += GUARD_TPB)
+    fold[i] = __hip_atomic_load(partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __syncthreads();
+  if (tid != 0) return;
+  *counter = 0;   // (reusable by the next launch)
+  double sum = 0.0;
+  for (int i = 0; i < nblk; ++i) sum += fold[i];
+  const float norm = (float)sqrt(sum);
+  int* gi = reinterpret_cast<int*>(guard);
+  const int policy = gi[GD_POLICY];
+  // torch.nn.utils.clip_grad_norm_: clip_coef = max_norm / (total_norm + 1e-6), clamped to 1 (a NaN stays a NaN)
+  float coef = 1.0f;
+  if (policy & GFV_GUARD_CLIP) {
+    const float c = guard[GD_MAX_NORM] / (norm + 1e-6f);
+    coef = (c < 1.0f || c != c) ? c : 1.0f;
+  }
+  int decision = 0;
+  const bool finite = fabsf(norm) <= 3.402823466e+38f;   // (false for inf and NaN)
+  if (!finite && (policy & GFV_GUARD_SKIP_NONFINITE)) decision |= GFV_GUARD_SKIP_NONFINITE;
+  if ((policy & GFV_GUARD_SKIP_FLAG) && *reinterpret_cast<const volatile int*>(status_dev) != 0) decision |= GFV_GUARD_SKIP_FLAG;
+  if (!decision && coef < 1.0f) decision = GFV_GUARD_CLIP;
+  guard[GD_NORM] = norm;
+  guard[GD_COEF] = coef;
+  gi[GD_DECISION] = decision;
+  if (decision & GFV_GUARD_CLIP) gi[GD_N_CLIPPED] += 1;
+  if (decision & GFV_GUARD_SKIP_NONFINITE) gi[GD_N_NONFINITE] += 1;
+  if (decision & GFV_GUARD_SKIP_FLAG) gi[GD_N_FLAG] += 1;
 }
 
 // loss = mean_b log(w_p*L_p + w_c*L_c + w_m*L_mx + w_m*L_my) (pre_train_Adam.py:177-184) and its gradient wrt the
@@ -568,8 +667,39 @@ extern "C" int gfv_adam_step_dev(float* p, const float* g, float* m, float* v, i
   int32_t* mirror = gfv_internal_status_mirror();
   long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
   if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  GFV_LAUNCH(adam_kernel, dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-             (const int*)gfv_internal_status_ptr(), (int*)mirror);
+  GFV_LAUNCH(adam_kernel<false>, dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
+             (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+extern "C" int gfv_adam_step_guarded_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state,
+                                         const float* hyper, const float* guard, void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, 28.0 * (double)n, stream);
+  if (!p || !g || !m || !v || n <= 0 || !state || !hyper || !guard) return GFV_ERR_ARG;
+  int32_t* mirror = gfv_internal_status_mirror();
+  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
+  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
+  GFV_LAUNCH(adam_kernel<true>, dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
+             (const int*)gfv_internal_status_ptr(), (int*)mirror, guard);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+// workspace = [arrival counter: int32 in an 8-byte header, zero between launches][GUARD_MAX_WGS partial sums: double]
+extern "C" size_t gfv_grad_guard_workspace_bytes(void) { return 8 + (size_t)GUARD_MAX_WGS * sizeof(double); }
+extern "C" int gfv_grad_guard_dev(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper,
+                                  float* guard, void* workspace, void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, 4.0 * (double)(n_elems > 0 ? n_elems : 0), stream);
+  if (!g || !segs || n_seg <= 0 || n_elems <= 0 || !hyper || !guard || !workspace || (reinterpret_cast<size_t>(workspace) & 7))
+    return GFV_ERR_ARG;
+  long wgs = ((long)n_elems + GUARD_TILE - 1) / GUARD_TILE;
+  if (wgs > GUARD_MAX_WGS) wgs = GUARD_MAX_WGS;
+  int* counter = reinterpret_cast<int*>(workspace);
+  double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + 8);
+  static_assert(sizeof(long) == sizeof(int64_t), "segment table words");
+  GFV_LAUNCH(grad_guard_kernel, dim3((unsigned)wgs), dim3(GUARD_TPB), 0, (hipStream_t)stream, g, reinterpret_cast<const long*>(segs),
+             (int)n_seg, hyper, guard, partials, counter, (const int*)gfv_internal_status_ptr());
   GFV_CHECK_LAUNCH();
   return GFV_OK;
 }

@@ -225,6 +225,10 @@ _SIGNATURES = {
     "gfv_node_prep": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "gfv_edge_attr": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "gfv_adam_step_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gfv_adam_step_guarded_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
+    "gfv_grad_guard_workspace_bytes": (C.c_size_t, []),
+    "gfv_grad_guard_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_prep_workspace_bytes": (C.c_size_t, [C.c_int32]),
     "gfv_prep_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -380,6 +384,7 @@ class limits:
         return False
 
 
+GUARD_CLIP, GUARD_SKIP_NONFINITE, GUARD_SKIP_FLAG = 1, 2, 4   # policy / decision bits of guard[8] (include/gfv.h gfv_grad_guard_dev)
 FLAG_NAMES = {1: "GFV_FLAG_DW_RANGE (a weight-gradient operand left the fp16 range)",
               2: "GFV_FLAG_CHAIN_RANGE (a hidden activation left the fixed-scale fp16 window of the column-owner chain kernels)"}
 _status_word = None

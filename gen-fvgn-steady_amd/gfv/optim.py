@@ -19,11 +19,14 @@ import torch
 
 from . import lib as L
 from .engine import GradStore
+from .guard import GradGuard, check_policy
 
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
-                 foreach=None, capturable=False, differentiable=False, fused=None, grad_scale=1.0):
+                 foreach=None, capturable=False, differentiable=False, fused=None, grad_scale=1.0, max_grad_norm=None,
+                 skip_nonfinite=False):
+        check_policy(max_grad_norm)
         if weight_decay != 0 or amsgrad or maximize or differentiable:
             raise NotImplementedError("gfv.optim.Adam: weight_decay=0, amsgrad=False, maximize=False only (torch.optim.Adam's "
                                       "defaults; the reference drivers use nothing else)")
@@ -48,6 +51,10 @@ class Adam(torch.optim.Optimizer):
         self.adam_state = torch.zeros(16, dtype=torch.float32, device=dev)
         self.hyper = torch.zeros(8, dtype=torch.float32, device=dev)
         self._grad_scale = float(grad_scale)
+        # training guard (gfv/guard.py): clip_grad_norm_ between backward() and step(), and "leave a non-finite step out", as two
+        # launches inside step().  Every parameter is a segment: one whose `.grad` is None has zeros in its slots (below), which
+        # add nothing to the norm - torch leaves it out
+        self._guard = GradGuard(self.G, dev, max_grad_norm, skip_nonfinite)
         self._hyper_host = None
         self._sync_hyper()
         L.status_mirror()   # the launch publishes the device status word (include/gfv.h gfv_status_mirror)
@@ -124,10 +131,29 @@ class Adam(torch.optim.Optimizer):
         g = self._flat_grad()
         if g is None:
             return loss
+        if self._guard.active:
+            self._guard.launch(self.flat_p, g, self.flat_m, self.flat_v, self.G.total, self.adam_state, self.hyper)
+            return loss
         L.check(L.load().gfv_adam_step_dev(self.flat_p.data_ptr(), g.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(),
                                            self.G.total, self.adam_state.data_ptr(), self.hyper.data_ptr(), L.stream_ptr()),
                 "adam_step")
         return loss
+
+    max_grad_norm = property(lambda self: self._guard.max_grad_norm)
+    skip_nonfinite = property(lambda self: self._guard.skip_nonfinite)
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        check_policy(v)
+        self._guard.set(v, self._guard.skip_nonfinite, False)
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, v):
+        self._guard.set(self._guard.max_grad_norm, v, False)
+
+    def guard_stats(self):
+        """As gfv.trainer.TrainStep.guard_stats (synchronises)."""
+        return self._guard.stats()
 
     # torch.optim.Adam's checkpoint nesting (importer.py:292-313 stores it under `optimizer0`) ---------------------------
     def state_dict(self):

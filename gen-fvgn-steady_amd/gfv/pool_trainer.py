@@ -41,6 +41,7 @@ import torch
 
 from . import cmdlist
 from . import lib as L
+from .guard import check_policy
 from .trainer import TrainStep
 
 _SCRATCH = ("_zero_e", "_dw_ws", "_dw_ws_main", "_prep_ws", "_fvm_cnt")
@@ -59,15 +60,18 @@ class PoolTrainStep(TrainStep):
     EVICT_MAX = 2
 
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
-                 use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None):
+                 use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
+                 skip_nonfinite=False, skip_on_flag=False):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
+        check_policy(max_grad_norm, skip_on_flag, bool(distributed))
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
         graphs, _ = self.arena.load([0])
         super().__init__(model, graphs, lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, world_size=1, use_graph=use_graph,
-                         want_outputs=want_outputs, distributed=distributed)
+                         want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
+                         skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = collections.OrderedDict()                    # key -> _Recorded, least recently used first

@@ -17,6 +17,7 @@ from . import cmdlist
 from . import lib as L
 from .engine import GradStore
 from .functions import unused_param_names
+from .guard import GradGuard, check_policy
 from .plan import _live_key, _refresh_live, get_plan
 
 
@@ -26,7 +27,9 @@ def _gather(src, index, out):
 
 class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
-                 process_group=None, use_graph=False, want_outputs=True, distributed=None):
+                 process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
+                 skip_nonfinite=False, skip_on_flag=False):
+        check_policy(max_grad_norm, skip_on_flag, (world_size > 1) if distributed is None else bool(distributed))
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -77,6 +80,9 @@ class TrainStep:
         self._setup_padding(names, tensors, skip)
         self._probes = [(names[i], tensors[i]) for i in sorted({0, len(names) // 2, len(names) - 1})]
         self.n_params = total
+        # training guard (gfv/guard.py): the device record the two guarded launches of _adam() read.  Its policy -
+        # max_grad_norm, skip_nonfinite, skip_on_flag - is mirrored into it on change; with all three off _adam() is one launch
+        self._guard = GradGuard(self.G, dev, max_grad_norm, skip_nonfinite, skip_on_flag)
         self.x = graphs[0].x
         self.x_backup = self.x.clone()
         B = self.plan.B
@@ -159,6 +165,41 @@ class TrainStep:
     def loss_weights(self, v):
         self._lw = tuple(float(x) for x in v)
         self._sync_hyper()
+
+    # the guard's policy: attributes like lr.  A new VALUE reaches recorded lists and captured graphs through the device record;
+    # only switching the guard as a whole on or off changes the launch sequence (one launch <-> two) and drops them.
+    max_grad_norm = property(lambda self: self._guard.max_grad_norm)
+    skip_nonfinite = property(lambda self: self._guard.skip_nonfinite)
+    skip_on_flag = property(lambda self: self._guard.skip_on_flag)
+
+    def _set_guard(self, **kw):
+        g = self._guard
+        new = dict(max_grad_norm=g.max_grad_norm, skip_nonfinite=g.skip_nonfinite, skip_on_flag=g.skip_on_flag)
+        new.update(kw)
+        check_policy(new["max_grad_norm"], new["skip_on_flag"], self.dist_on)
+        was = g.active
+        g.set(**new)
+        if g.active != was:
+            self._graphs.clear()
+            self._list_warm.clear()
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        self._set_guard(max_grad_norm=v)
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, v):
+        self._set_guard(skip_nonfinite=v)
+
+    @skip_on_flag.setter
+    def skip_on_flag(self, v):
+        self._set_guard(skip_on_flag=v)
+
+    def guard_stats(self):
+        """{"norm", "coef", "decision", "clipped", "skipped_nonfinite", "skipped_flag"} of the guard: the last guarded step's
+        gradient norm (after the all-reduce and the 1 / world scale), clip coefficient and decision bits (gfv.lib.GUARD_*), and
+        the running counts.  Synchronises: for logging every so often, not every step.  Not part of state_dict()."""
+        return self._guard.stats()
 
     def set_lr(self, lr):
         """What `lr_scheduler.step()` does to the reference's optimizer; eager and hipGraph steps both follow it."""
@@ -275,6 +316,11 @@ class TrainStep:
             self._adam()
 
     def _adam(self):
+        if self._guard.active:
+            # two launches: the global norm of the gradient + the decision (clip coefficient, apply or not) into the device
+            # record, then the Adam that obeys it - no host decision, so lists and graphs replay it like any other launch
+            self._guard.launch(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper)
+            return
         # ONE launch (round 6): its last workgroup advances the step count, forms the next step's bias corrections and publishes
         # the device status word into the pinned mirror `step()` reads (include/gfv.h gfv_adam_step_dev, gfv_status_mirror)
         L.check(L.load().gfv_adam_step_dev(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
@@ -446,11 +492,11 @@ class TrainStep:
     # state snapshot so the capture warm-up does not advance training ---------------------------------------
     def _snapshot(self):
         nb = self.model.node_norm
-        self._snap = (self.flat_p.clone(), self.flat_m.clone(), self.flat_v.clone(), self.adam_state.clone(),
+        self._snap = (self.flat_p.clone(), self.flat_m.clone(), self.flat_v.clone(), self.adam_state.clone(), self._guard.guard.clone(),
                       nb.acc_count.clone(), nb.num_accumulations.clone(), nb.acc_sum.clone(), nb.acc_sum_squared.clone())
 
     def _restore(self):
         nb = self.model.node_norm
-        for dst, src in zip((self.flat_p, self.flat_m, self.flat_v, self.adam_state, nb.acc_count, nb.num_accumulations,
-                             nb.acc_sum, nb.acc_sum_squared), self._snap):
+        for dst, src in zip((self.flat_p, self.flat_m, self.flat_v, self.adam_state, self._guard.guard, nb.acc_count,
+                             nb.num_accumulations, nb.acc_sum, nb.acc_sum_squared), self._snap):
             dst.copy_(src)

@@ -582,6 +582,36 @@ int gfv_prep_apply(const float* x_raw, float* x_out, const int32_t* batch, const
 int gfv_adam_state_init(float* state, double beta1, double beta2, float steps_done, void* stream);
 int gfv_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
                       void* stream);
+/* Training guard: clip by global norm and leave bad steps out, decided on the device - no host decision, so recorded
+ * launch lists and captured graphs keep replaying.  Two launches in place of gfv_adam_step_dev:
+ *
+ * gfv_grad_guard_dev: ONE launch.  norm = sqrt(sum over the segments of (g[i] * hyper[4])^2): `segs` is a DEVICE table of n_seg
+ *   (offset, count) int64 pairs into g - the elements torch would see; nothing outside a segment is read (alignment padding,
+ *   slots of parameters without a gradient may hold anything, NaN included).  n_elems = the sum of the counts (it sizes the
+ *   grid).  The sum is accumulated in double in a fixed order (no floating-point atomics: same inputs, same bits), each workgroup
+ *   leaves one partial in `workspace` and the one that arrives last adds them in index order and writes the decision:
+ *   guard[8], 32-bit words (float unless marked):
+ *     [0] max_norm            host-written; read when GFV_GUARD_CLIP is set
+ *     [1] policy   (int32)    host-written: OR of GFV_GUARD_CLIP | GFV_GUARD_SKIP_NONFINITE | GFV_GUARD_SKIP_FLAG
+ *     [2] norm                of the last launch, rounded once from double
+ *     [3] coef                fp32 max_norm / (norm + 1e-6f) where that is below 1 or NaN, else exactly 1.0f (clip_grad_norm_'s
+ *                             formula); exactly 1.0f without GFV_GUARD_CLIP
+ *     [4] decision (int32)    0 = applied as it is; GFV_GUARD_CLIP = applied with coef < 1; GFV_GUARD_SKIP_NONFINITE (the norm is
+ *                             inf or NaN and the policy bit is set) and / or GFV_GUARD_SKIP_FLAG (the device status word is
+ *                             non-zero and the policy bit is set; the word is read, not cleared) = no step
+ *     [5] [6] [7]  (int32)    running counts of launches whose decision carried GFV_GUARD_CLIP, .._SKIP_NONFINITE, .._SKIP_FLAG
+ *   workspace: gfv_grad_guard_workspace_bytes() bytes, 8-byte aligned, ZEROED once by the caller (its first word is the arrival
+ *   counter, left zero by every launch); one workspace per stream of guard launches.
+ * gfv_adam_step_guarded_dev: gfv_adam_step_dev with gi = (g[i] * grad_scale) * guard[3]; with a skip bit in guard[4] it writes
+ *   nothing to p, m, v and does not advance state[0] or the running powers (the arrival counter is still reset and the status
+ *   word still published).  With coef == 1.0f and no skip its results are those of gfv_adam_step_dev bit for bit.
+ * Both return GFV_ERR_ARG (nothing launched) on a NULL pointer, n / n_seg / n_elems < 1 or a misaligned workspace. */
+enum { GFV_GUARD_CLIP = 1, GFV_GUARD_SKIP_NONFINITE = 2, GFV_GUARD_SKIP_FLAG = 4 };
+size_t gfv_grad_guard_workspace_bytes(void);
+int gfv_grad_guard_dev(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper, float* guard,
+                       void* workspace, void* stream);
+int gfv_adam_step_guarded_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
+                              const float* guard, void* stream);
 int gfv_train_loss(const float* losses, int32_t B, float w_cont, float w_mom, float w_press, float* loss, float* gloss,
                    void* stream);
 /* same, weights read from the device: hyper[5..7] = {w_cont, w_mom, w_press} of the buffer gfv_adam_step_dev takes */
