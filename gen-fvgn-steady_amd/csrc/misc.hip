@@ -396,11 +396,14 @@ enum { GD_MAX_NORM = 0, GD_POLICY = 1, GD_NORM = 2, GD_COEF = 3, GD_DECISION = 4
 constexpr int ADAM_TPB = 512, ADAM_MAX_WGS = 512;   // (few workgroups: one same-address atomic each at the end)
 // GUARDED: the step of gfv_adam_step_guarded_dev - the gradient times the clip coefficient of guard[], or no step at all.
 // The plain form (GUARDED = false, guard unused) is the kernel it has always been.
-template <bool GUARDED>
+// ACCUM: the step of gfv_adam_step_accum_dev - behind a gfv_grad_accum_dev launch that did not close its accumulation
+// (accum[AC_APPLY] == 0, a hold micro-step) it is a skipped step: nothing written, t and the powers stay, status word published.
+enum { AC_STEPS = 0, AC_MICRO = 1, AC_GRAPHS = 2, AC_APPLY = 3, AC_LOSS_SUM = 4, AC_LOSS_MEAN = 5, AC_CLOSED = 6, AC_COUNTER = 7 };
+template <bool GUARDED, bool ACCUM>
 __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                         float* __restrict__ v, long n, float* state,
                                                         const float* __restrict__ hyper, const int* status_dev, int* status_host,
-                                                        const float* __restrict__ guard) {
+                                                        const float* __restrict__ guard, const float* __restrict__ accum) {
   const float step_size = (float)((double)hyper[0] / as_get(state, AS_BC1_HI)), bc2_sqrt = state[AS_SQRT_BC2];
   const float t_done = state[AS_T];
   const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], grad_scale = hyper[4];
@@ -411,6 +414,7 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
     coef = guard[GD_COEF];
     skip = (reinterpret_cast<const int*>(guard)[GD_DECISION] & (GFV_GUARD_SKIP_NONFINITE | GFV_GUARD_SKIP_FLAG)) != 0;
   }
+  if constexpr (ACCUM) skip = skip || reinterpret_cast<const int*>(accum)[AC_APPLY] == 0;
   if (!skip) {
     for (long i = (long)blockIdx.x * ADAM_TPB + threadIdx.x; i < n; i += (long)gridDim.x * ADAM_TPB) {
       float gi = g[i] * grad_scale;
@@ -451,13 +455,18 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
 // The hand-off of the partials carries no fence, for the reason written above adam_kernel (the backward has just dirtied the
 // L2 with the gradient): thread 0 stores its workgroup's partial write-through (an agent-scope atomic store), waits for that
 // store, then adds to the arrival counter; the last arriver reads the partials with agent-scope loads that bypass its L1.
+// ACCUM (gfv_grad_guard_accum_dev): on a hold micro-step every workgroup leaves at once - no norm, no decision, no count.
 constexpr int GUARD_TPB = 256, GUARD_PER_THREAD = 4, GUARD_TILE = GUARD_TPB * GUARD_PER_THREAD, GUARD_MAX_WGS = 256;
+template <bool ACCUM>
 __global__ __launch_bounds__(GUARD_TPB) void grad_guard_kernel(const float* __restrict__ g, const long* __restrict__ segs, int n_seg,
                                                                const float* __restrict__ hyper, float* guard, double* partials,
-                                                               int* counter, const int* status_dev) {
+                                                               int* counter, const int* status_dev, const float* __restrict__ accum) {
   __shared__ double red[GUARD_TPB / 64];
   __shared__ double fold[GUARD_MAX_WGS];
   __shared__ int last;
+  if constexpr (ACCUM) {
+    if (reinterpret_cast<const int*>(accum)[AC_APPLY] == 0) return;
+  }
   const int tid = threadIdx.x, blk = blockIdx.x, nblk = gridDim.x;
   const float grad_scale = hyper[4];
   double acc = 0.0;
@@ -520,6 +529,71 @@ __global__ __launch_bounds__(GUARD_TPB) void grad_guard_kernel(const float* __re
   if (decision & GFV_GUARD_CLIP) gi[GD_N_CLIPPED] += 1;
   if (decision & GFV_GUARD_SKIP_NONFINITE) gi[GD_N_NONFINITE] += 1;
   if (decision & GFV_GUARD_SKIP_FLAG) gi[GD_N_FLAG] += 1;
+}
+
+// Gradient accumulation (include/gfv.h gfv_grad_accum_dev): one launch over the flat gradient between the
+// backward and the norm / Adam launches.  The phase comes from the device record - first (micro == 0): acc = B g, acc not read;
+// middle: acc += B g; last (micro == steps - 1): g = (acc + B g) / (graphs + B), acc not written - so one recorded list serves
+// every micro-step.  Every workgroup reads the record before its loop; the one that arrives last (the arrival pattern of
+// adam_kernel: relaxed, no fence - it needs no data of the others, only that they are past their reads) advances it.
+constexpr int ACC_TPB = 256, ACC_MAX_WGS = 512;
+__global__ __launch_bounds__(ACC_TPB) void grad_accum_kernel(float* __restrict__ g, float* __restrict__ acc, long n, int B,
+                                                             const float* __restrict__ loss, float* accum) {
+  int* rec = reinterpret_cast<int*>(accum);
+  const int steps = rec[AC_STEPS], micro = rec[AC_MICRO], graphs = rec[AC_GRAPHS];
+  const bool first = micro <= 0, last = micro >= steps - 1;
+  const float fb = (float)B, denom = (float)((first ? 0 : graphs) + B);   // (a first micro-step trusts nothing an earlier one left)
+  // 16 bytes per lane where both buffers allow it; the tail (n % 4 elements, or everything of a misaligned buffer) by element
+  const bool wide = ((reinterpret_cast<size_t>(g) | reinterpret_cast<size_t>(acc)) & 15) == 0;
+  const long n4 = wide ? (n >> 2) : 0;
+  const long stride = (long)gridDim.x * ACC_TPB, t0 = (long)blockIdx.x * ACC_TPB + threadIdx.x;
+  float4* g4 = reinterpret_cast<float4*>(g);
+  float4* a4 = reinterpret_cast<float4*>(acc);
+  if (last) {
+    for (long i = t0; i < n4; i += stride) {
+      const float4 x = g4[i];
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (!first) a = a4[i];
+      float4 r;
+      if (first) { r.x = fb * x.x; r.y = fb * x.y; r.z = fb * x.z; r.w = fb * x.w; }
+      else { r.x = a.x + fb * x.x; r.y = a.y + fb * x.y; r.z = a.z + fb * x.z; r.w = a.w + fb * x.w; }
+      g4[i] = make_float4(r.x / denom, r.y / denom, r.z / denom, r.w / denom);
+    }
+    for (long i = 4 * n4 + t0; i < n; i += stride) g[i] = (first ? fb * g[i] : acc[i] + fb * g[i]) / denom;
+  } else if (first) {
+    for (long i = t0; i < n4; i += stride) {
+      const float4 x = g4[i];
+      a4[i] = make_float4(fb * x.x, fb * x.y, fb * x.z, fb * x.w);
+    }
+    for (long i = 4 * n4 + t0; i < n; i += stride) acc[i] = fb * g[i];
+  } else {
+    for (long i = t0; i < n4; i += stride) {
+      const float4 x = g4[i], a = a4[i];
+      a4[i] = make_float4(a.x + fb * x.x, a.y + fb * x.y, a.z + fb * x.z, a.w + fb * x.w);
+    }
+    for (long i = 4 * n4 + t0; i < n; i += stride) acc[i] = acc[i] + fb * g[i];
+  }
+  __syncthreads();   // every thread of this workgroup is past its reads of the record (they chose the branch above)
+  if (threadIdx.x == 0) {
+    if (__hip_atomic_fetch_add(rec + AC_COUNTER, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
+      rec[AC_COUNTER] = 0;
+      const float part = fb * *loss;
+      const float sum = first ? part : accum[AC_LOSS_SUM] + part;
+      if (last) {
+        accum[AC_LOSS_MEAN] = sum / denom;
+        rec[AC_CLOSED] += 1;
+        rec[AC_MICRO] = 0;
+        rec[AC_GRAPHS] = 0;
+        accum[AC_LOSS_SUM] = 0.f;
+        rec[AC_APPLY] = 1;
+      } else {
+        rec[AC_MICRO] = (first ? 0 : micro) + 1;
+        rec[AC_GRAPHS] = (first ? 0 : graphs) + B;
+        accum[AC_LOSS_SUM] = sum;
+        rec[AC_APPLY] = 0;
+      }
+    }
+  }
 }
 
 // loss = mean_b log(w_p*L_p + w_c*L_c + w_m*L_mx + w_m*L_my) (pre_train_Adam.py:177-184) and its gradient wrt the
@@ -667,8 +741,8 @@ extern "C" int gfv_adam_step_dev(float* p, const float* g, float* m, float* v, i
   int32_t* mirror = gfv_internal_status_mirror();
   long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
   if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  GFV_LAUNCH(adam_kernel<false>, dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-             (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr);
+  GFV_LAUNCH((adam_kernel<false, false>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
+             (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr, (const float*)nullptr);
   GFV_CHECK_LAUNCH();
   return GFV_OK;
 }
@@ -680,28 +754,69 @@ extern "C" int gfv_adam_step_guarded_dev(float* p, const float* g, float* m, flo
   int32_t* mirror = gfv_internal_status_mirror();
   long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
   if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  GFV_LAUNCH(adam_kernel<true>, dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-             (const int*)gfv_internal_status_ptr(), (int*)mirror, guard);
+  GFV_LAUNCH((adam_kernel<true, false>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
+             (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, (const float*)nullptr);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+// the Adam launch behind gfv_grad_accum_dev: guard == NULL is the plain step, else the guarded one; either obeys accum[3]
+extern "C" int gfv_adam_step_accum_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
+                                       const float* guard, const float* accum, void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, 28.0 * (double)n, stream);
+  if (!p || !g || !m || !v || n <= 0 || !state || !hyper || !accum) return GFV_ERR_ARG;
+  int32_t* mirror = gfv_internal_status_mirror();
+  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
+  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
+  if (guard)
+    GFV_LAUNCH((adam_kernel<true, true>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
+               (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, accum);
+  else
+    GFV_LAUNCH((adam_kernel<false, true>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
+               (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr, accum);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+extern "C" int gfv_grad_accum_dev(float* g, float* acc, int64_t n, int32_t B, const float* loss, float* accum, void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, 12.0 * (double)(n > 0 ? n : 0), stream);   // g, acc in; one of them out
+  if (!g || !acc || n < 0 || B < 1 || !loss || !accum) return GFV_ERR_ARG;
+  long wgs = ((n >> 2) + ACC_TPB - 1) / ACC_TPB;
+  if (wgs > ACC_MAX_WGS) wgs = ACC_MAX_WGS;
+  if (wgs < 1) wgs = 1;   // (n < 4: the tail alone; n == 0: the record still advances)
+  GFV_LAUNCH(grad_accum_kernel, dim3((unsigned)wgs), dim3(ACC_TPB), 0, (hipStream_t)stream, g, acc, (long)n, (int)B, loss, accum);
   GFV_CHECK_LAUNCH();
   return GFV_OK;
 }
 
 // workspace = [arrival counter: int32 in an 8-byte header, zero between launches][GUARD_MAX_WGS partial sums: double]
 extern "C" size_t gfv_grad_guard_workspace_bytes(void) { return 8 + (size_t)GUARD_MAX_WGS * sizeof(double); }
-extern "C" int gfv_grad_guard_dev(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper,
-                                  float* guard, void* workspace, void* stream) {
+namespace {
+template <bool ACCUM>
+int grad_guard_launch(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper, float* guard,
+                      void* workspace, const float* accum, void* stream) {
   GfvProfScope ps_(GFV_K_MISC, 0, 4.0 * (double)(n_elems > 0 ? n_elems : 0), stream);
   if (!g || !segs || n_seg <= 0 || n_elems <= 0 || !hyper || !guard || !workspace || (reinterpret_cast<size_t>(workspace) & 7))
     return GFV_ERR_ARG;
+  if (ACCUM && !accum) return GFV_ERR_ARG;
   long wgs = ((long)n_elems + GUARD_TILE - 1) / GUARD_TILE;
   if (wgs > GUARD_MAX_WGS) wgs = GUARD_MAX_WGS;
   int* counter = reinterpret_cast<int*>(workspace);
   double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + 8);
   static_assert(sizeof(long) == sizeof(int64_t), "segment table words");
-  GFV_LAUNCH(grad_guard_kernel, dim3((unsigned)wgs), dim3(GUARD_TPB), 0, (hipStream_t)stream, g, reinterpret_cast<const long*>(segs),
-             (int)n_seg, hyper, guard, partials, counter, (const int*)gfv_internal_status_ptr());
+  GFV_LAUNCH(grad_guard_kernel<ACCUM>, dim3((unsigned)wgs), dim3(GUARD_TPB), 0, (hipStream_t)stream, g, reinterpret_cast<const long*>(segs),
+             (int)n_seg, hyper, guard, partials, counter, (const int*)gfv_internal_status_ptr(), accum);
   GFV_CHECK_LAUNCH();
   return GFV_OK;
+}
+}  // namespace
+extern "C" int gfv_grad_guard_dev(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper,
+                                  float* guard, void* workspace, void* stream) {
+  return grad_guard_launch<false>(g, segs, n_seg, n_elems, hyper, guard, workspace, nullptr, stream);
+}
+extern "C" int gfv_grad_guard_accum_dev(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper,
+                                        float* guard, void* workspace, const float* accum, void* stream) {
+  return grad_guard_launch<true>(g, segs, n_seg, n_elems, hyper, guard, workspace, accum, stream);
 }
 
 extern "C" int gfv_train_loss(const float* losses, int32_t B, float w_cont, float w_mom, float w_press, float* loss,

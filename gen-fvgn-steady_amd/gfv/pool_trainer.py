@@ -18,6 +18,11 @@ that were recorded - no host-side decision of `Engine.forward / backward` reads 
 steps first, as `TrainStep` does), later ones replay; the cache is bounded by the bytes of the lists' private memory pools,
 least recently used out (a key evicted EVICT_MAX times stays eager: it would otherwise record on every visit).  The recorded list contains only the step; assembly and payback are issued around the replay.
 
+Gradient accumulation (`accum_steps=k`, gfv/accum.py): k consecutive `step()` calls are one optimiser step over the
+mean gradient of all their graphs.  The key of a list is unchanged: the launches behind the backward are the same on every
+micro-step and read their phase from a device record, so the list of a signature is replayed in every phase.  With micro-batches
+of one or two meshes a pool of N sizes has N or N^2 ordered signatures instead of N^8, and every list is small.
+
 Who owns what a recorded list points at.  (1) The list's own private memory pool: activations and outputs.  (2) The arena: every
 plan tensor, the normalised `x` and the un-normalised state the input preparation reads (`x_raw=`).  (3) The flat parameter /
 gradient / moment buffers, `loss`, the per-B `gloss`, the Adam state: this object, for its lifetime.  (4) The engine's
@@ -41,6 +46,7 @@ import torch
 
 from . import cmdlist
 from . import lib as L
+from .accum import check_accum_steps
 from .guard import check_policy
 from .trainer import TrainStep
 
@@ -61,17 +67,18 @@ class PoolTrainStep(TrainStep):
 
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
-                 skip_nonfinite=False, skip_on_flag=False):
+                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
+        check_accum_steps(accum_steps, bool(distributed))
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
         graphs, _ = self.arena.load([0])
         super().__init__(model, graphs, lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, world_size=1, use_graph=use_graph,
                          want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
-                         skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag)
+                         skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = collections.OrderedDict()                    # key -> _Recorded, least recently used first
@@ -198,6 +205,8 @@ class PoolTrainStep(TrainStep):
                         self._oversize.add(old)
         if acc:
             self.model.node_norm.note_accumulated()
+        if self._accum is not None:
+            self._accum.note_step()
         if payback or advance:
             if self.uvp_node is None:
                 raise RuntimeError("payback needs the prediction of the step (want_outputs=True)")

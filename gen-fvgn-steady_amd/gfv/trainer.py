@@ -15,6 +15,7 @@ import torch
 
 from . import cmdlist
 from . import lib as L
+from .accum import GradAccum, check_accum_steps
 from .engine import GradStore
 from .functions import unused_param_names
 from .guard import GradGuard, check_policy
@@ -28,8 +29,9 @@ def _gather(src, index, out):
 class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
-                 skip_nonfinite=False, skip_on_flag=False):
+                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1):
         check_policy(max_grad_norm, skip_on_flag, (world_size > 1) if distributed is None else bool(distributed))
+        accum_steps = check_accum_steps(accum_steps, (world_size > 1) if distributed is None else bool(distributed))
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -83,6 +85,8 @@ class TrainStep:
         # training guard (gfv/guard.py): the device record the two guarded launches of _adam() read.  Its policy -
         # max_grad_norm, skip_nonfinite, skip_on_flag - is mirrored into it on change; with all three off _adam() is one launch
         self._guard = GradGuard(self.G, dev, max_grad_norm, skip_nonfinite, skip_on_flag)
+        # gradient accumulation (gfv/accum.py): None with accum_steps == 1 - no second buffer, _adam() as it was
+        self._accum = GradAccum(total, dev, accum_steps) if accum_steps > 1 else None
         self.x = graphs[0].x
         self.x_backup = self.x.clone()
         B = self.plan.B
@@ -195,6 +199,42 @@ class TrainStep:
     def skip_on_flag(self, v):
         self._set_guard(skip_on_flag=v)
 
+    # gradient accumulation: `accum_steps` is an attribute like lr.  A new value is mirrored into the device record and drops the
+    # open accumulation; only a change between 1 and more than 1 changes the launch sequence and drops lists and graphs.
+    @property
+    def accum_steps(self):
+        return 1 if self._accum is None else self._accum.steps
+
+    @accum_steps.setter
+    def accum_steps(self, v):
+        v = check_accum_steps(v, self.dist_on)
+        if v == self.accum_steps:
+            return
+        if (v > 1) != (self._accum is not None):
+            self._accum = GradAccum(self.n_params, self.dev, v) if v > 1 else None
+            self._graphs.clear()
+            self._list_warm.clear()
+        else:
+            self._accum.set_steps(v)
+
+    @property
+    def accum_pending(self):
+        """Micro-steps taken in the open accumulation (host count; the device count depends on nothing but the steps issued)."""
+        return 0 if self._accum is None else self._accum.pending
+
+    def accum_reset(self):
+        """Drop an open accumulation: the next step is the first micro-step of a new one."""
+        if self._accum is not None:
+            self._accum.reset()
+
+    def accum_stats(self):
+        """{"micro", "graphs", "loss_mean", "closed"} of the device record: micro-steps and graphs of the open accumulation, the
+        mean loss over the graphs of the last closed one, the number closed.  Synchronises: for logging, like guard_stats().
+        Not part of state_dict(): an open accumulation is not state."""
+        if self._accum is None:
+            return {"micro": 0, "graphs": 0, "loss_mean": float("nan"), "closed": 0}
+        return self._accum.stats()
+
     def guard_stats(self):
         """{"norm", "coef", "decision", "clipped", "skipped_nonfinite", "skipped_flag"} of the guard: the last guarded step's
         gradient norm (after the all-reduce and the 1 / world scale), clip coefficient and decision bits (gfv.lib.GUARD_*), and
@@ -248,6 +288,7 @@ class TrainStep:
             self._lw = tuple(float(x) for x in sd["gfv_loss_weights"])
         self._sync_hyper()
         self._init_adam_state(0.0 if step is None else step)
+        self.accum_reset()
 
     def named_state(self):
         """{name: (parameter, exp_avg, exp_avg_sq)} views of the flat buffers.  (The alignment padding between tensors is not
@@ -316,6 +357,12 @@ class TrainStep:
             self._adam()
 
     def _adam(self):
+        if self._accum is not None:
+            # three launches, the same on every micro-step: fold this gradient into the accumulator (or, closing, the mean back
+            # into flat_g), then the norm (guard on) and the Adam that do nothing unless the first one closed the accumulation
+            self._accum.launch(self._guard, self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.plan.B,
+                               self.loss, self.adam_state, self.hyper)
+            return
         if self._guard.active:
             # two launches: the global norm of the gradient + the decision (clip coefficient, apply or not) into the device
             # record, then the Adam that obeys it - no host decision, so lists and graphs replay it like any other launch
@@ -487,6 +534,8 @@ class TrainStep:
                 self._adam()
         if acc:
             self.model.node_norm.note_accumulated()
+        if self._accum is not None:
+            self._accum.note_step()
         return self.loss
 
     # state snapshot so the capture warm-up does not advance training ---------------------------------------
@@ -494,9 +543,12 @@ class TrainStep:
         nb = self.model.node_norm
         self._snap = (self.flat_p.clone(), self.flat_m.clone(), self.flat_v.clone(), self.adam_state.clone(), self._guard.guard.clone(),
                       nb.acc_count.clone(), nb.num_accumulations.clone(), nb.acc_sum.clone(), nb.acc_sum_squared.clone())
+        if self._accum is not None:
+            self._snap += (self._accum.acc.clone(), self._accum.rec.clone())
 
     def _restore(self):
         nb = self.model.node_norm
         for dst, src in zip((self.flat_p, self.flat_m, self.flat_v, self.adam_state, self._guard.guard, nb.acc_count,
-                             nb.num_accumulations, nb.acc_sum, nb.acc_sum_squared), self._snap):
+                             nb.num_accumulations, nb.acc_sum, nb.acc_sum_squared)
+                            + (() if self._accum is None else (self._accum.acc, self._accum.rec)), self._snap):
             dst.copy_(src)

@@ -612,6 +612,42 @@ int gfv_grad_guard_dev(const float* g, const int64_t* segs, int32_t n_seg, int64
                        void* workspace, void* stream);
 int gfv_adam_step_guarded_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
                               const float* guard, void* stream);
+/* Gradient accumulation: k micro-batches, one optimiser step.  Three launches in place of the one or two above,
+ * the same three on every micro-step - which of them does what is decided on the device, so ONE recorded list or captured
+ * graph per batch signature serves all phases.
+ *
+ * gfv_grad_accum_dev: ONE launch over g[0, n) (n = the whole flat gradient, alignment padding included: harmless, as for Adam).
+ *   acc: a second buffer of n floats; B >= 1: the graph count of this micro-batch; loss: the step's device scalar.
+ *   accum[8], 32-bit words:
+ *     [0] steps     (int32)   k, host-written
+ *     [1] micro     (int32)   micro-steps taken in the open accumulation, 0 .. k - 1
+ *     [2] graphs    (int32)   graphs summed so far
+ *     [3] apply     (int32)   1 if this launch closed an accumulation, else 0
+ *     [4] loss_sum            sum of B_i * loss_i of the open accumulation (0 after a close)
+ *     [5] loss_mean           loss_sum / graphs of the last closed accumulation
+ *     [6] closed    (int32)   running count of closed accumulations
+ *     [7]           (int32)   arrival counter, zero between launches
+ *   The caller zeroes the record once and writes [0]; to drop an open accumulation it zeroes [1], [2] and [4].
+ *   first  (micro == 0):         acc[i] = B * g[i]; acc is NOT read (what an abandoned accumulation left there cannot leak)
+ *   middle:                      acc[i] = acc[i] + B * g[i]
+ *   last   (micro == steps - 1): g[i] = (acc[i] + B * g[i]) / (graphs + B), the mean over all graphs, written into g for the
+ *                                unchanged norm / Adam arithmetic behind it; acc is not written.  (steps == 1: g = B * g / B.)
+ *   fp32, product and sum rounded separately.  Every workgroup reads the record before anything in it is written; the one that
+ *   arrives last (relaxed integer counter [7], no fence, no floating-point atomics: same inputs, same bits) writes [1] .. [4] and,
+ *   on a close, [5], [6], micro = graphs = 0.  16-byte accesses where g and acc are 16-byte aligned, by element otherwise and
+ *   for the n % 4 tail.
+ * gfv_grad_guard_accum_dev: gfv_grad_guard_dev that, with accum[3] == 0 (a hold micro-step), leaves guard[2..7] untouched; with
+ *   accum[3] == 1 its results are those of gfv_grad_guard_dev bit for bit.
+ * gfv_adam_step_accum_dev: gfv_adam_step_dev (guard == NULL) or gfv_adam_step_guarded_dev (guard given) that, with accum[3] == 0,
+ *   writes nothing to p, m, v and does not advance state[0] or the running powers (arrival counter reset, status word
+ *   published, as a skipped step); with accum[3] == 1 the results of those entry points bit for bit.
+ * All three return GFV_ERR_ARG (nothing launched) on a NULL pointer (the optional guard apart), n < 0 (accumulate) or n < 1
+ * (Adam), B < 1, and what gfv_grad_guard_dev refuses. */
+int gfv_grad_accum_dev(float* g, float* acc, int64_t n, int32_t B, const float* loss, float* accum, void* stream);
+int gfv_grad_guard_accum_dev(const float* g, const int64_t* segs, int32_t n_seg, int64_t n_elems, const float* hyper, float* guard,
+                             void* workspace, const float* accum, void* stream);
+int gfv_adam_step_accum_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
+                            const float* guard, const float* accum, void* stream);
 int gfv_train_loss(const float* losses, int32_t B, float w_cont, float w_mom, float w_press, float* loss, float* gloss,
                    void* stream);
 /* same, weights read from the device: hyper[5..7] = {w_cont, w_mom, w_press} of the buffer gfv_adam_step_dev takes */
