@@ -399,11 +399,32 @@ constexpr int ADAM_TPB = 512, ADAM_MAX_WGS = 512;   // (few workgroups: one same
 // ACCUM: the step of gfv_adam_step_accum_dev - behind a gfv_grad_accum_dev launch that did not close its accumulation
 // (accum[AC_APPLY] == 0, a hold micro-step) it is a skipped step: nothing written, t and the powers stay, status word published.
 enum { AC_STEPS = 0, AC_MICRO = 1, AC_GRAPHS = 2, AC_APPLY = 3, AC_LOSS_SUM = 4, AC_LOSS_MEAN = 5, AC_CLOSED = 6, AC_COUNTER = 7 };
-template <bool GUARDED, bool ACCUM>
-__global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, long n, float* state,
-                                                        const float* __restrict__ hyper, const int* status_dev, int* status_host,
-                                                        const float* __restrict__ guard, const float* __restrict__ accum) {
+// EMA: the step of gfv_adam_step_ema_dev - an exponential moving average e of the parameters, updated with the new p[i] still in
+// its register: e[i] = fmaf(w, p_new - e[i], e[i]), w = ema[EM_W] read by every thread before its loop.  The workgroup that
+// arrives last counts the update and writes the weight of the next one (ema_weight below: the one statement of the formula).
+// A step that is not applied (guard skip, hold micro-step) writes neither e nor the record.
+enum { EM_DECAY = 0, EM_WARMUP = 1, EM_UPDATES = 2, EM_W = 3 };
+// weight of the update that follows k applied ones: 1 - decay, or with warmup 1 - min(decay, (1 + k) / (10 + k)); fp32 throughout
+__device__ __forceinline__ float ema_weight(float decay, int warmup, int k) {
+  float d = decay;
+  if (warmup) d = fminf(decay, (1.0f + (float)k) / (10.0f + (float)k));
+  return 1.0f - d;
+}
+__global__ void ema_init_kernel(float* ema, float decay, int warmup, int updates) {
+  int* rec = reinterpret_cast<int*>(ema);
+  for (int i = 0; i < 8; ++i) rec[i] = 0;
+  ema[EM_DECAY] = decay;
+  rec[EM_WARMUP] = warmup;
+  rec[EM_UPDATES] = updates;
+  ema[EM_W] = ema_weight(decay, warmup, updates);
+}
+
+// (the body of adam_kernel and adam_ema_kernel; EMA = false compiles to the kernel without the average, e and ema unused)
+template <bool GUARDED, bool ACCUM, bool EMA>
+__device__ __forceinline__ void adam_step(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, long n, float* state, const float* __restrict__ hyper,
+                                          const int* status_dev, int* status_host, const float* __restrict__ guard,
+                                          const float* __restrict__ accum, float* __restrict__ e, float* ema) {
   const float step_size = (float)((double)hyper[0] / as_get(state, AS_BC1_HI)), bc2_sqrt = state[AS_SQRT_BC2];
   const float t_done = state[AS_T];
   const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], grad_scale = hyper[4];
@@ -415,6 +436,8 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
     skip = (reinterpret_cast<const int*>(guard)[GD_DECISION] & (GFV_GUARD_SKIP_NONFINITE | GFV_GUARD_SKIP_FLAG)) != 0;
   }
   if constexpr (ACCUM) skip = skip || reinterpret_cast<const int*>(accum)[AC_APPLY] == 0;
+  float w = 0.f;
+  if constexpr (EMA) w = ema[EM_W];
   if (!skip) {
     for (long i = (long)blockIdx.x * ADAM_TPB + threadIdx.x; i < n; i += (long)gridDim.x * ADAM_TPB) {
       float gi = g[i] * grad_scale;
@@ -423,7 +446,12 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
       const float vi = v[i] * b2 + omb2 * gi * gi;
       m[i] = mi; v[i] = vi;
       const float denom = sqrtf(vi) / bc2_sqrt + eps;
-      p[i] = p[i] - step_size * (mi / denom);
+      const float pi = p[i] - step_size * (mi / denom);
+      p[i] = pi;
+      if constexpr (EMA) {
+        const float ei = e[i];
+        e[i] = fmaf(w, pi - ei, ei);
+      }
     }
   }
   __syncthreads();   // every thread of this workgroup has read the state (the values were consumed by the loop above)
@@ -437,6 +465,12 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
       if (!skip) {   // (a skipped step is no step: t and the running powers stay)
         state[AS_T] = t_done + 1.0f;
         adam_corrections(state, as_get(state, AS_P1) * as_get(state, AS_B1), as_get(state, AS_P2) * as_get(state, AS_B2));
+        if constexpr (EMA) {   // (every workgroup is past its read of ema[EM_W], as of the state)
+          int* rec = reinterpret_cast<int*>(ema);
+          const int k = rec[EM_UPDATES] + 1;
+          rec[EM_UPDATES] = k;
+          ema[EM_W] = ema_weight(ema[EM_DECAY], rec[EM_WARMUP], k);
+        }
       }
       if (status_host) {
         const int f = *reinterpret_cast<const volatile int*>(status_dev);
@@ -444,6 +478,21 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
       }
     }
   }
+}
+template <bool GUARDED, bool ACCUM>
+__global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, long n, float* state,
+                                                        const float* __restrict__ hyper, const int* status_dev, int* status_host,
+                                                        const float* __restrict__ guard, const float* __restrict__ accum) {
+  adam_step<GUARDED, ACCUM, false>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, nullptr, nullptr);
+}
+template <bool GUARDED, bool ACCUM>
+__global__ __launch_bounds__(ADAM_TPB) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, long n, float* state,
+                                                            const float* __restrict__ hyper, const int* status_dev, int* status_host,
+                                                            const float* __restrict__ guard, const float* __restrict__ accum,
+                                                            float* __restrict__ e, float* ema) {
+  adam_step<GUARDED, ACCUM, true>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, e, ema);
 }
 
 // Global L2 norm of the scaled gradient over a table of (offset, count) segments of the flat buffer, and the decision the
@@ -774,6 +823,35 @@ extern "C" int gfv_adam_step_accum_dev(float* p, const float* g, float* m, float
   else
     GFV_LAUNCH((adam_kernel<false, true>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
                (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr, accum);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+// Averaged weights (include/gfv.h): the record's four words, w by the one device statement of its formula
+extern "C" int gfv_ema_init(float* ema, float decay, int32_t warmup, int32_t updates, void* stream) {
+  if (!ema || !(decay >= 0.f && decay < 1.f) || (warmup != 0 && warmup != 1) || updates < 0) return GFV_ERR_ARG;
+  GFV_LAUNCH(ema_init_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, ema, decay, (int)warmup, (int)updates);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+// the Adam launch of any of the three forms above (guard, accum: each NULL or given) that also advances the average e
+extern "C" int gfv_adam_step_ema_dev(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* state,
+                                     const float* hyper, const float* guard, const float* accum, float* ema, void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, 36.0 * (double)n, stream);   // p, g, m, v, e in; p, m, v, e out
+  if (!p || !g || !m || !v || !e || n <= 0 || !state || !hyper || !ema) return GFV_ERR_ARG;
+  if (e < p + n && p < e + n) return GFV_ERR_ARG;   // (e == p among them: the average would be the iterate)
+  int32_t* mirror = gfv_internal_status_mirror();
+  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
+  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
+#define GFV_ADAM_EMA(G, A)                                                                                                        \
+  GFV_LAUNCH((adam_ema_kernel<G, A>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper, \
+             (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, accum, e, ema)
+  if (guard && accum) GFV_ADAM_EMA(true, true);
+  else if (guard) GFV_ADAM_EMA(true, false);
+  else if (accum) GFV_ADAM_EMA(false, true);
+  else GFV_ADAM_EMA(false, false);
+#undef GFV_ADAM_EMA
   GFV_CHECK_LAUNCH();
   return GFV_OK;
 }

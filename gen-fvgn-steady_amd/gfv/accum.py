@@ -48,8 +48,9 @@ class GradAccum:
     def note_step(self):
         self.pending = (self.pending + 1) % self.steps
 
-    def launch(self, guard, p, g, m, v, n, B, loss, state, hyper):
-        """The accumulate launch, the hold-aware norm + decision launch where the guard is active, the hold-aware Adam."""
+    def launch(self, guard, p, g, m, v, n, B, loss, state, hyper, ema=None):
+        """The accumulate launch, the hold-aware norm + decision launch where the guard is active, the hold-aware Adam (ema: a
+        gfv.ema.WeightEMA - the hold-aware Adam that also advances the average on a closing micro-step)."""
         lib, st = L.load(), L.stream_ptr()
         rec = self.rec.data_ptr()
         L.check(lib.gfv_grad_accum_dev(g.data_ptr(), self.acc.data_ptr(), n, int(B), loss.data_ptr(), rec, st), "grad_accum")
@@ -58,6 +59,9 @@ class GradAccum:
             gptr = guard.guard.data_ptr()
             L.check(lib.gfv_grad_guard_accum_dev(g.data_ptr(), guard.segs.data_ptr(), guard.n_seg, guard.n_elems, hyper.data_ptr(),
                                                  gptr, guard.ws.data_ptr(), rec, st), "grad_guard_accum")
+        if ema is not None:
+            ema.launch(p, g, m, v, n, state, hyper, guard=None if gptr is None else guard.guard, accum=self.rec)
+            return
         L.check(lib.gfv_adam_step_accum_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, state.data_ptr(),
                                             hyper.data_ptr(), gptr, rec, st), "adam_step_accum")
 

@@ -66,11 +66,15 @@ class GradGuard:
             self._host = vals
         self.active = policy != 0
 
-    def launch(self, p, g, m, v, n, state, hyper):
-        """The norm + decision launch, then the Adam launch that obeys it."""
+    def launch(self, p, g, m, v, n, state, hyper, ema=None):
+        """The norm + decision launch, then the Adam launch that obeys it (ema: a gfv.ema.WeightEMA - the Adam launch that also
+        advances the average, where the step is applied)."""
         lib, st = L.load(), L.stream_ptr()
         L.check(lib.gfv_grad_guard_dev(g.data_ptr(), self.segs.data_ptr(), self.n_seg, self.n_elems, hyper.data_ptr(),
                                        self.guard.data_ptr(), self.ws.data_ptr(), st), "grad_guard")
+        if ema is not None:
+            ema.launch(p, g, m, v, n, state, hyper, guard=self.guard)
+            return
         L.check(lib.gfv_adam_step_guarded_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, state.data_ptr(),
                                               hyper.data_ptr(), self.guard.data_ptr(), st), "adam_step_guarded")
 

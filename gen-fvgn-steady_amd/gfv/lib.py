@@ -232,6 +232,9 @@ _SIGNATURES = {
                                            C.c_void_p]),
     "gfv_adam_step_accum_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "gfv_ema_init": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
+    "gfv_adam_step_ema_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_grad_guard_workspace_bytes": (C.c_size_t, []),
     "gfv_grad_guard_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_prep_workspace_bytes": (C.c_size_t, [C.c_int32]),

@@ -47,6 +47,7 @@ import torch
 from . import cmdlist
 from . import lib as L
 from .accum import check_accum_steps
+from .ema import check_ema
 from .guard import check_policy
 from .trainer import TrainStep
 
@@ -67,18 +68,20 @@ class PoolTrainStep(TrainStep):
 
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
-                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1):
+                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
         check_accum_steps(accum_steps, bool(distributed))
+        check_ema(ema_decay, ema_warmup)
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
         graphs, _ = self.arena.load([0])
         super().__init__(model, graphs, lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, world_size=1, use_graph=use_graph,
                          want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
-                         skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps)
+                         skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
+                         ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = collections.OrderedDict()                    # key -> _Recorded, least recently used first
@@ -142,6 +145,7 @@ class PoolTrainStep(TrainStep):
         """One training iteration over the pool entries `indices` -> the (device) scalar loss tensor.
         payback: write the predicted (u, v, p) back into the entries' own `x` (one launch); advance: also into the arena's raw
         state, so that the next inner step over the SAME batch starts from it (`TrainStep.advance_time`)."""
+        self._not_swapped("step()")
         self._check_aliasing()
         L.raise_on_status("PoolTrainStep.step")
         idx = [int(i) for i in indices]

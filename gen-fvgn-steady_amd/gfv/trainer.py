@@ -9,6 +9,7 @@ a hipGraph (torch.cuda.CUDAGraph) to remove host launch overhead.
 """
 from __future__ import annotations
 
+import contextlib
 import os
 
 import torch
@@ -16,6 +17,7 @@ import torch
 from . import cmdlist
 from . import lib as L
 from .accum import GradAccum, check_accum_steps
+from .ema import WeightEMA, check_ema
 from .engine import GradStore
 from .functions import unused_param_names
 from .guard import GradGuard, check_policy
@@ -29,9 +31,10 @@ def _gather(src, index, out):
 class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
-                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1):
+                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True):
         check_policy(max_grad_norm, skip_on_flag, (world_size > 1) if distributed is None else bool(distributed))
         accum_steps = check_accum_steps(accum_steps, (world_size > 1) if distributed is None else bool(distributed))
+        ema_decay = check_ema(ema_decay, ema_warmup)
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -87,6 +90,9 @@ class TrainStep:
         self._guard = GradGuard(self.G, dev, max_grad_norm, skip_nonfinite, skip_on_flag)
         # gradient accumulation (gfv/accum.py): None with accum_steps == 1 - no second buffer, _adam() as it was
         self._accum = GradAccum(total, dev, accum_steps) if accum_steps > 1 else None
+        # averaged weights (gfv/ema.py): None with ema_decay None - no third buffer, _adam() as it was
+        self._ema_warmup = bool(ema_warmup)
+        self._ema = WeightEMA(self.flat_p, total, ema_decay, self._ema_warmup) if ema_decay is not None else None
         self.x = graphs[0].x
         self.x_backup = self.x.clone()
         B = self.plan.B
@@ -235,6 +241,81 @@ class TrainStep:
             return {"micro": 0, "graphs": 0, "loss_mean": float("nan"), "closed": 0}
         return self._accum.stats()
 
+    # averaged weights: `ema_decay` and `ema_warmup` are attributes like lr.  A new value goes to the device record through
+    # gfv_ema_init and keeps the update count; only a change between None and a value changes the launch sequence and drops lists
+    # and graphs (and starts the average from the current parameters).
+    @property
+    def ema_decay(self):
+        return None if self._ema is None else self._ema.decay
+
+    @ema_decay.setter
+    def ema_decay(self, v):
+        v = check_ema(v, self._ema_warmup)
+        if v == self.ema_decay:
+            return
+        self._not_swapped("ema_decay")
+        if (v is None) != (self._ema is None):
+            self._ema = WeightEMA(self.flat_p, self.n_params, v, self._ema_warmup) if v is not None else None
+            self._graphs.clear()
+            self._list_warm.clear()
+        else:
+            self._ema.set(v, self._ema_warmup)
+
+    @property
+    def ema_warmup(self):
+        return self._ema_warmup
+
+    @ema_warmup.setter
+    def ema_warmup(self, v):
+        v = bool(v)
+        if v != self._ema_warmup and self._ema is not None:
+            self._ema.set(self._ema.decay, v)
+        self._ema_warmup = v
+
+    def _need_ema(self, what):
+        if self._ema is None:
+            raise RuntimeError(f"{what} needs the averaged weights (ema_decay=...)")
+        return self._ema
+
+    def _not_swapped(self, what):
+        if self._ema is not None and self._ema.swapped:
+            raise RuntimeError(f"{what} inside `with ema_weights():` - the model holds the averaged weights, not the iterate")
+
+    def ema_reset(self):
+        """The average restarts from the current parameters, the update count (and with it the warmup) from zero."""
+        self._not_swapped("ema_reset()")
+        if self._ema is not None:
+            self._ema.reset(self.flat_p)
+
+    def ema_stats(self):
+        """{"decay", "warmup", "updates", "w"} of the device record: `updates` counts the optimiser steps that were applied (not
+        the skipped ones, not the hold micro-steps), `w` is the weight of the next update.  Synchronises."""
+        if self._ema is None:
+            return {"decay": None, "warmup": self._ema_warmup, "updates": 0, "w": float("nan")}
+        return self._ema.stats()
+
+    def ema_parameters(self):
+        """{name: CPU tensor} of the averaged weights, named and shaped as `model.param_names_tensors()` (no alignment padding)."""
+        ema = self._need_ema("ema_parameters()")
+        src = (self.flat_p if ema.swapped else ema.e).detach().cpu()
+        return {n: src[self.G.off[n]:self.G.off[n] + self.G.numel(n)].view(self.G.shape[n]).clone() for n in self.G.off}
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the block the model holds the averaged weights: the CONTENTS of the parameters - views of flat_p - and of the
+        average change places, so the model carries them at the addresses every recorded list and every Rollout / Sweep points
+        at (their WeightGuard sees the in-place change: `refresh_weights()` first).  Swapped back on exit; no step() inside."""
+        ema = self._need_ema("ema_weights()")
+        self._not_swapped("ema_weights()")
+        self._check_aliasing()
+        names, tensors = self.model.param_names_tensors()
+        offsets = [self.G.off[n] for n in names]
+        ema.swap(tensors, offsets)
+        try:
+            yield self
+        finally:
+            ema.swap(tensors, offsets)
+
     def guard_stats(self):
         """{"norm", "coef", "decision", "clipped", "skipped_nonfinite", "skipped_flag"} of the guard: the last guarded step's
         gradient norm (after the all-reduce and the 1 / world scale), clip coefficient and decision bits (gfv.lib.GUARD_*), and
@@ -265,9 +346,16 @@ class TrainStep:
                         "exp_avg_sq": self.flat_v[off:off + k].view(self.G.shape[n]).detach().cpu().clone()}
         group = {"lr": self._lr, "betas": self._betas, "eps": self._eps, "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group], "gfv_param_names": names, "gfv_loss_weights": self._lw}
+        sd = {"state": state, "param_groups": [group], "gfv_param_names": names, "gfv_loss_weights": self._lw}
+        if self._ema is not None:
+            # (a top-level key torch.optim.Adam.load_state_dict ignores, as it does the two above)
+            avg = self.ema_parameters()
+            sd["gfv_ema"] = {"decay": self._ema.decay, "warmup": self._ema.warmup, "updates": self._ema.stats()["updates"],
+                             "params": [avg[n] for n in names]}
+        return sd
 
     def load_state_dict(self, sd):
+        self._not_swapped("load_state_dict()")
         names = list(self.G.off)
         if "gfv_param_names" in sd and list(sd["gfv_param_names"]) != names:
             raise ValueError("optimizer state belongs to a different parameter set")
@@ -289,6 +377,16 @@ class TrainStep:
         self._sync_hyper()
         self._init_adam_state(0.0 if step is None else step)
         self.accum_reset()
+        if self._ema is not None:
+            # (the model was loaded before the optimiser: without an average in the dict it restarts from the loaded weights)
+            self._ema.reset(self.flat_p)
+            avg = sd.get("gfv_ema")
+            if avg is not None:
+                for n, t in zip(names, avg["params"]):
+                    off, k = self.G.off[n], self.G.numel(n)
+                    self._ema.e[off:off + k].copy_(t.reshape(-1))
+                self._ema_warmup = bool(avg["warmup"])
+                self._ema.set(check_ema(avg["decay"]), self._ema_warmup, int(avg["updates"]))
 
     def named_state(self):
         """{name: (parameter, exp_avg, exp_avg_sq)} views of the flat buffers.  (The alignment padding between tensors is not
@@ -357,6 +455,9 @@ class TrainStep:
             self._adam()
 
     def _adam(self):
+        if self._ema is not None:
+            self._adam_ema()
+            return
         if self._accum is not None:
             # three launches, the same on every micro-step: fold this gradient into the accumulator (or, closing, the mean back
             # into flat_g), then the norm (guard on) and the Adam that do nothing unless the first one closed the accumulation
@@ -373,6 +474,17 @@ class TrainStep:
         L.check(L.load().gfv_adam_step_dev(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
                                            self.flat_v.data_ptr(), self.n_params, self.adam_state.data_ptr(),
                                            self.hyper.data_ptr(), L.stream_ptr()), "adam_step")
+
+    def _adam_ema(self):
+        """The three branches of _adam() with the averaged weights on: the same launches in front, and in the place of each
+        branch's Adam launch the one that also advances the average (gfv_adam_step_ema_dev) - where the step is applied."""
+        args = (self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params)
+        if self._accum is not None:
+            self._accum.launch(self._guard, *args, self.plan.B, self.loss, self.adam_state, self.hyper, ema=self._ema)
+        elif self._guard.active:
+            self._guard.launch(*args, self.adam_state, self.hyper, ema=self._ema)
+        else:
+            self._ema.launch(*args, self.adam_state, self.hyper)
 
     # data-parallel exchange: the flat gradient is reduced in two buckets.  The upper one (last processor + decoder:
     # their backward runs first) goes out on a communication stream as soon as its last gradient kernel is launched and
@@ -452,6 +564,7 @@ class TrainStep:
     def step(self):
         """One training iteration.  Returns the (device) scalar loss tensor of this rank's batch.
         `use_graph`: False = eager launches, True = hipGraph replay, "list" = command-list replay."""
+        self._not_swapped("step()")
         self._check_aliasing()
         # what the kernels of the steps BEFORE the last one raised in the device status word (a hidden activation outside the
         # fixed-scale fp16 window, a weight-gradient operand beyond fp16): read from the pinned mirror the fused Adam publishes
@@ -545,10 +658,13 @@ class TrainStep:
                       nb.acc_count.clone(), nb.num_accumulations.clone(), nb.acc_sum.clone(), nb.acc_sum_squared.clone())
         if self._accum is not None:
             self._snap += (self._accum.acc.clone(), self._accum.rec.clone())
+        if self._ema is not None:
+            self._snap += (self._ema.e.clone(), self._ema.rec.clone())
 
     def _restore(self):
         nb = self.model.node_norm
         for dst, src in zip((self.flat_p, self.flat_m, self.flat_v, self.adam_state, self._guard.guard, nb.acc_count,
                              nb.num_accumulations, nb.acc_sum, nb.acc_sum_squared)
-                            + (() if self._accum is None else (self._accum.acc, self._accum.rec)), self._snap):
+                            + (() if self._accum is None else (self._accum.acc, self._accum.rec))
+                            + (() if self._ema is None else (self._ema.e, self._ema.rec)), self._snap):
             dst.copy_(src)

@@ -648,6 +648,31 @@ int gfv_grad_guard_accum_dev(const float* g, const int64_t* segs, int32_t n_seg,
                              void* workspace, const float* accum, void* stream);
 int gfv_adam_step_accum_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
                             const float* guard, const float* accum, void* stream);
+/* Averaged weights: an exponential moving average e of the parameters, advanced inside the Adam launch with the new
+ * parameter value still in its register - one more stream (read e, write e: 36 bytes per element instead of 28), no launch.
+ *   ema[8], 32-bit words:
+ *     [0] decay              host-written (through gfv_ema_init), in [0, 1)
+ *     [1] warmup   (int32)   0 or 1, host-written (through gfv_ema_init)
+ *     [2] updates  (int32)   number of updates applied to e so far; after gfv_ema_init only the device advances it
+ *     [3] w                  weight of the NEXT update: 1 - d_eff, with d_eff = decay (warmup 0) or
+ *                            min(decay, (1 + updates) / (10 + updates)) (warmup 1: the average follows a young run closely and
+ *                            reaches `decay` at updates = (10 decay - 1) / (1 - decay)); fp32: the quotient, the minimum and the
+ *                            difference each rounded once
+ *     [4..7]                 zero
+ * gfv_ema_init: ONE thread writes all eight words for the given decay, warmup and update count - the formula of w exists in one
+ *   place on the device, this launch and the Adam launch below call it.  GFV_ERR_ARG (nothing launched) on a NULL record, a decay
+ *   that is NaN or outside [0, 1), a warmup other than 0 or 1, updates < 0.
+ * gfv_adam_step_ema_dev: gfv_adam_step_dev (guard == NULL, accum == NULL), gfv_adam_step_guarded_dev (guard given),
+ *   gfv_adam_step_accum_dev (accum given, guard optional) - the same template, p, m, v and state bit for bit what those entry
+ *   points leave - that also does, per element and with p_new the value it has just stored to p[i],
+ *       e[i] = fmaf(w, p_new - e[i], e[i])        (fp32; the difference rounded once, product and sum rounded together)
+ *   with w = ema[3] as every thread read it before its loop.  e: n floats that do not overlap p[0, n).  The workgroup that arrives
+ *   last at state[4] (the Adam launch's own relaxed arrival counter: no fence, no second counter) then does updates += 1 and
+ *   writes the next w.  A step that is not applied - a skip bit in guard[4], accum[3] == 0 - writes neither e nor ema[2], ema[3].
+ *   GFV_ERR_ARG (nothing launched) on a NULL pointer (guard and accum apart), n < 1, or e overlapping p (e == p included). */
+int gfv_ema_init(float* ema, float decay, int32_t warmup, int32_t updates, void* stream);
+int gfv_adam_step_ema_dev(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* state, const float* hyper,
+                          const float* guard, const float* accum, float* ema, void* stream);
 int gfv_train_loss(const float* losses, int32_t B, float w_cont, float w_mom, float w_press, float* loss, float* gloss,
                    void* stream);
 /* same, weights read from the device: hyper[5..7] = {w_cont, w_mom, w_press} of the buffer gfv_adam_step_dev takes */
