@@ -419,13 +419,46 @@ __global__ void ema_init_kernel(float* ema, float decay, int warmup, int updates
   ema[EM_W] = ema_weight(decay, warmup, updates);
 }
 
-// (the body of adam_kernel and adam_ema_kernel; EMA = false compiles to the kernel without the average, e and ema unused)
-template <bool GUARDED, bool ACCUM, bool EMA>
+// Parameter groups (include/gfv.h gfv_adam_step_groups_dev): the step above with a rate, a weight decay and a
+// "leave this alone" per GROUP of parameter tensors.  Two device tables say which element belongs to which group: the run table -
+// one run per tensor of the flat layout, run_start[r] ascending and closed by run_start[n_runs] = n (a tensor's alignment padding
+// belongs to its run), run_group[r] its row - and the group table: a header row {n_groups, decoupled, 0...} (int32) and
+// GFV_MAX_PARAM_GROUPS + 1 rows of 8 words {lr, weight_decay, flags (int32), 0...}; the last row is reserved and always frozen
+// (parameters without a gradient point at it).  No per-element stream of group ids: a workgroup stages the run starts in LDS
+// (at most GRP_LDS_RUNS of them: the entry point refuses a longer table), a thread bisects once per sweep - from its current run
+// upwards, and only when its element has left that run - and forms step size and decay factor again when the run changed.
+// A frozen element is neither read nor written (p, m, v, e).  The arithmetic of a live element with weight_decay == 0 is the
+// statement sequence of the other forms: one live group without decay gives the bits of GROUPS = false, which compiles to the
+// kernels that have always been there (run_start, run_group, groups and the LDS table unused).
+enum { GT_N_GROUPS = 0, GT_DECOUPLED = 1, GR_LR = 0, GR_WD = 1, GR_FLAGS = 2 };
+constexpr int GRP_LDS_RUNS = GFV_MAX_PARAM_RUNS;
+__device__ __forceinline__ int adam_find_run(const long* starts, int lo, int hi, long i) {   // starts[r] <= i < starts[r + 1], r in [lo, hi]
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (starts[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+// (the body of adam_kernel, adam_ema_kernel and adam_groups_kernel; EMA = false compiles to the kernel without the average, e and
+// ema unused; GROUPS = false to the kernel without the tables)
+template <bool GUARDED, bool ACCUM, bool EMA, bool GROUPS>
 __device__ __forceinline__ void adam_step(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                           float* __restrict__ v, long n, float* state, const float* __restrict__ hyper,
                                           const int* status_dev, int* status_host, const float* __restrict__ guard,
-                                          const float* __restrict__ accum, float* __restrict__ e, float* ema) {
-  const float step_size = (float)((double)hyper[0] / as_get(state, AS_BC1_HI)), bc2_sqrt = state[AS_SQRT_BC2];
+                                          const float* __restrict__ accum, float* __restrict__ e, float* ema,
+                                          const long* __restrict__ run_start = nullptr, const int* __restrict__ run_group = nullptr,
+                                          int n_runs = 0, const float* __restrict__ groups = nullptr, long* s_start = nullptr) {
+  bool decoupled = false;
+  if constexpr (GROUPS) {
+    for (int r = threadIdx.x; r <= n_runs; r += ADAM_TPB) s_start[r] = run_start[r];   // (n_runs <= GRP_LDS_RUNS: the entry point)
+    __syncthreads();
+    decoupled = reinterpret_cast<const int*>(groups)[GT_DECOUPLED] != 0;
+  }
+  const double bc1 = as_get(state, AS_BC1_HI);
+  float step_size = 0.f;   // (GROUPS: from the group's lr at every run change; hyper[0] is not read)
+  if constexpr (!GROUPS) step_size = (float)((double)hyper[0] / bc1);
+  const float bc2_sqrt = state[AS_SQRT_BC2];
   const float t_done = state[AS_T];
   const float b1 = hyper[1], b2 = hyper[2], eps = hyper[3], grad_scale = hyper[4];
   const float omb1 = state[AS_OMB1], omb2 = state[AS_OMB2];
@@ -439,14 +472,41 @@ __device__ __forceinline__ void adam_step(float* __restrict__ p, const float* __
   float w = 0.f;
   if constexpr (EMA) w = ema[EM_W];
   if (!skip) {
+    int run = -1;
+    long run_end = 0;   // (GROUPS: the first element is outside "the current run", the first trip searches from run 0)
+    float wd = 0.f, keep = 1.0f;
+    bool frozen = false;
     for (long i = (long)blockIdx.x * ADAM_TPB + threadIdx.x; i < n; i += (long)gridDim.x * ADAM_TPB) {
+      if constexpr (GROUPS) {
+        if (i >= run_end) {
+          const int lo = run + 1, hi = n_runs - 1;
+          run = lo >= hi ? hi : adam_find_run(s_start, lo, hi, i);
+          run_end = s_start[run + 1];
+          int grp = run_group[run];
+          grp = grp < 0 ? 0 : (grp > GFV_MAX_PARAM_GROUPS ? GFV_MAX_PARAM_GROUPS : grp);
+          const float* row = groups + 8 * (1 + grp);
+          const float lr = row[GR_LR];
+          wd = row[GR_WD];
+          frozen = grp == GFV_MAX_PARAM_GROUPS || (reinterpret_cast<const int*>(row)[GR_FLAGS] & GFV_GROUP_FROZEN) != 0;
+          step_size = (float)((double)lr / bc1);
+          keep = (float)(1.0 - (double)lr * (double)wd);   // (torch forms 1 - lr * weight_decay on the host, in double)
+        }
+        if (frozen) continue;   // neither read nor written: p, m, v, e
+      }
       float gi = g[i] * grad_scale;
       if constexpr (GUARDED) gi = gi * coef;
+      float pold = p[i];
+      if constexpr (GROUPS) {
+        if (wd != 0.f) {
+          if (decoupled) pold = pold * keep;
+          else gi = gi + wd * pold;
+        }
+      }
       const float mi = m[i] * b1 + omb1 * gi;
       const float vi = v[i] * b2 + omb2 * gi * gi;
       m[i] = mi; v[i] = vi;
       const float denom = sqrtf(vi) / bc2_sqrt + eps;
-      const float pi = p[i] - step_size * (mi / denom);
+      const float pi = pold - step_size * (mi / denom);
       p[i] = pi;
       if constexpr (EMA) {
         const float ei = e[i];
@@ -484,7 +544,7 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_kernel(float* __restrict__ p, c
                                                         float* __restrict__ v, long n, float* state,
                                                         const float* __restrict__ hyper, const int* status_dev, int* status_host,
                                                         const float* __restrict__ guard, const float* __restrict__ accum) {
-  adam_step<GUARDED, ACCUM, false>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, nullptr, nullptr);
+  adam_step<GUARDED, ACCUM, false, false>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, nullptr, nullptr);
 }
 template <bool GUARDED, bool ACCUM>
 __global__ __launch_bounds__(ADAM_TPB) void adam_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -492,7 +552,19 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_ema_kernel(float* __restrict__ 
                                                             const float* __restrict__ hyper, const int* status_dev, int* status_host,
                                                             const float* __restrict__ guard, const float* __restrict__ accum,
                                                             float* __restrict__ e, float* ema) {
-  adam_step<GUARDED, ACCUM, true>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, e, ema);
+  adam_step<GUARDED, ACCUM, true, false>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, e, ema);
+}
+template <bool GUARDED, bool ACCUM, bool EMA>
+__global__ __launch_bounds__(ADAM_TPB) void adam_groups_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                               float* __restrict__ v, long n, float* state,
+                                                               const float* __restrict__ hyper, const int* status_dev, int* status_host,
+                                                               const float* __restrict__ guard, const float* __restrict__ accum,
+                                                               float* __restrict__ e, float* ema, const long* __restrict__ run_start,
+                                                               const int* __restrict__ run_group, int n_runs,
+                                                               const float* __restrict__ groups) {
+  __shared__ long s_start[GRP_LDS_RUNS + 1];
+  adam_step<GUARDED, ACCUM, EMA, true>(p, g, m, v, n, state, hyper, status_dev, status_host, guard, accum, e, ema, run_start, run_group,
+                                       n_runs, groups, s_start);
 }
 
 // Global L2 norm of the scaled gradient over a table of (offset, count) segments of the flat buffer, and the decision the
@@ -852,6 +924,41 @@ extern "C" int gfv_adam_step_ema_dev(float* p, const float* g, float* m, float* 
   else if (accum) GFV_ADAM_EMA(false, true);
   else GFV_ADAM_EMA(false, false);
 #undef GFV_ADAM_EMA
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+// the Adam launch of any of the forms above (guard, accum, e + ema: each NULL or given) with per-group rate, decay and freezing
+extern "C" int gfv_adam_step_groups_dev(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* state,
+                                        const float* hyper, const float* guard, const float* accum, float* ema,
+                                        const int64_t* run_start, const int32_t* run_group, int32_t n_runs, const float* groups,
+                                        void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, (e ? 36.0 : 28.0) * (double)n, stream);
+  if (!p || !g || !m || !v || n <= 0 || !state || !hyper || !run_start || !run_group || n_runs < 1 ||
+      n_runs > GRP_LDS_RUNS || !groups)
+    return GFV_ERR_ARG;
+  if ((e == nullptr) != (ema == nullptr)) return GFV_ERR_ARG;
+  if (e && e < p + n && p < e + n) return GFV_ERR_ARG;
+  int32_t* mirror = gfv_internal_status_mirror();
+  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
+  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
+  static_assert(sizeof(long) == sizeof(int64_t), "run table words");
+#define GFV_ADAM_GROUPS(G, A, E)                                                                                                     \
+  GFV_LAUNCH((adam_groups_kernel<G, A, E>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, \
+             hyper, (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, accum, e, ema,                                      \
+             reinterpret_cast<const long*>(run_start), (const int*)run_group, (int)n_runs, groups)
+  const int form = (guard ? 4 : 0) | (accum ? 2 : 0) | (e ? 1 : 0);
+  switch (form) {
+    case 0: GFV_ADAM_GROUPS(false, false, false); break;
+    case 1: GFV_ADAM_GROUPS(false, false, true); break;
+    case 2: GFV_ADAM_GROUPS(false, true, false); break;
+    case 3: GFV_ADAM_GROUPS(false, true, true); break;
+    case 4: GFV_ADAM_GROUPS(true, false, false); break;
+    case 5: GFV_ADAM_GROUPS(true, false, true); break;
+    case 6: GFV_ADAM_GROUPS(true, true, false); break;
+    default: GFV_ADAM_GROUPS(true, true, true); break;
+  }
+#undef GFV_ADAM_GROUPS
   GFV_CHECK_LAUNCH();
   return GFV_OK;
 }

@@ -24,13 +24,14 @@ def check_policy(max_grad_norm, skip_on_flag=False, dist_on=False):
                          "disagree on whether the step is applied")
 
 
-def segments(store):
+def segments(store, exclude=()):
     """(offset, count) of every run of gradient elements of `store` (a gfv.engine.GradStore) that belongs to a used parameter:
-    no alignment padding, no parameter of `store.skip`; neighbours without a gap are merged."""
+    no alignment padding, no parameter of `store.skip` or of `exclude` (the frozen parameter groups, gfv/groups.py: torch's
+    clip_grad_norm_ would not see them); neighbours without a gap are merged."""
     segs = []
     for n, off in store.off.items():
         k = store.numel(n)
-        if n in store.skip or k == 0:
+        if n in store.skip or n in exclude or k == 0:
             continue
         if segs and segs[-1][0] + segs[-1][1] == off:
             segs[-1][1] += k
@@ -43,16 +44,22 @@ class GradGuard:
     FIELDS = ("norm", "coef", "decision", "clipped", "skipped_nonfinite", "skipped_flag")
 
     def __init__(self, store, device, max_grad_norm=None, skip_nonfinite=False, skip_on_flag=False):
-        segs = segments(store)
-        if not segs:
-            raise ValueError("no parameter with a gradient: nothing to guard")
-        self.n_seg, self.n_elems = len(segs), sum(k for _, k in segs)
-        self.segs = torch.tensor(segs, dtype=torch.int64).reshape(-1).to(device)
+        self.device = device
+        self.set_segments(store)
         self.guard = torch.zeros(8, dtype=torch.float32, device=device)
         ws = int(L.load(raw=True).gfv_grad_guard_workspace_bytes())
         self.ws = torch.zeros((ws + 7) // 8, dtype=torch.float64, device=device)
         self._host = None
         self.set(max_grad_norm, skip_nonfinite, skip_on_flag)
+
+    def set_segments(self, store, exclude=()):
+        """The segment table of `store` without the parameters of `exclude`.  A NEW table: the owner drops its recorded lists and
+        captured graphs (they hold the old one's address and length)."""
+        segs = segments(store, exclude)
+        if not segs:
+            raise ValueError("no parameter with a gradient: nothing to guard")
+        self.n_seg, self.n_elems = len(segs), sum(k for _, k in segs)
+        self.segs = torch.tensor(segs, dtype=torch.int64).reshape(-1).to(self.device)
 
     def set(self, max_grad_norm, skip_nonfinite, skip_on_flag):
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)

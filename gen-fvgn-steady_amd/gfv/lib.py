@@ -235,6 +235,8 @@ _SIGNATURES = {
     "gfv_ema_init": (C.c_int, [C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     "gfv_adam_step_ema_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gfv_adam_step_groups_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "gfv_grad_guard_workspace_bytes": (C.c_size_t, []),
     "gfv_grad_guard_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_prep_workspace_bytes": (C.c_size_t, [C.c_int32]),
@@ -392,6 +394,7 @@ class limits:
         return False
 
 
+MAX_PARAM_GROUPS, MAX_PARAM_RUNS, GROUP_FROZEN = 32, 1024, 1   # GFV_MAX_PARAM_GROUPS, GFV_MAX_PARAM_RUNS, GFV_GROUP_FROZEN (include/gfv.h gfv_adam_step_groups_dev)
 GUARD_CLIP, GUARD_SKIP_NONFINITE, GUARD_SKIP_FLAG = 1, 2, 4   # policy / decision bits of guard[8] (include/gfv.h gfv_grad_guard_dev)
 FLAG_NAMES = {1: "GFV_FLAG_DW_RANGE (a weight-gradient operand left the fp16 range)",
               2: "GFV_FLAG_CHAIN_RANGE (a hidden activation left the fixed-scale fp16 window of the column-owner chain kernels)"}

@@ -6,8 +6,12 @@ tensors (pre_train_Adam.py:79,191; solve_with_grad_GPU.py:181).
 What it does to the model: the parameters become views of one flat buffer (16-byte aligned, in the order they were given - as
 `gfv.trainer.TrainStep` lays them out); `NNmodel`'s backward hands out gradients as views of one flat tensor in the same
 layout, which `step()` recognises and feeds to the kernel as it is (otherwise the gradients are gathered into a flat buffer
-first: still one optimiser launch).  Supported: one parameter group, `weight_decay=0`, `amsgrad=False`, `maximize=False`
-(torch.optim.Adam's defaults, what both reference drivers use); anything else raises at construction.
+first: still one optimiser launch).  Parameter groups with their own `lr` and `weight_decay` (L2 as torch.optim.Adam,
+decoupled as `AdamW` / `decoupled_weight_decay=True`) and the extra group key `"frozen": True` run inside the same launch
+(gfv/groups.py, include/gfv.h gfv_adam_step_groups_dev); with one group, no decay and nothing frozen the launches are the ones
+without groups.  Refused at construction: `amsgrad`, `maximize`, `differentiable`, groups whose `betas` or `eps` differ (the step
+record is shared).  The step count is shared too: a parameter that starts to move after k steps (a group unfrozen, a `.grad` that
+was None) continues with count k + 1 and zero moments, where torch, counting per parameter, starts its bias correction at 1.
 
 `gfv.optim.LBFGS` - torch.optim.LBFGS for the closure loop of solve_with_grad_GPU_LBFGS.py:67-202, the same way: one import
 changed, the same flat buffer, and the search direction in four launches (csrc/lbfgs.hip) instead of ~4 m launches and 2 m host
@@ -19,23 +23,33 @@ import torch
 
 from . import lib as L
 from .engine import GradStore
+from .groups import MAX_GROUPS, ParamGroups, check_weight_decay
 from .guard import GradGuard, check_policy
 
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, maximize=False,
-                 foreach=None, capturable=False, differentiable=False, fused=None, grad_scale=1.0, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False, grad_scale=1.0,
+                 max_grad_norm=None, skip_nonfinite=False):
         check_policy(max_grad_norm)
-        if weight_decay != 0 or amsgrad or maximize or differentiable:
-            raise NotImplementedError("gfv.optim.Adam: weight_decay=0, amsgrad=False, maximize=False only (torch.optim.Adam's "
-                                      "defaults; the reference drivers use nothing else)")
-        defaults = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=0, amsgrad=False,
-                        maximize=False)
+        if amsgrad:
+            raise NotImplementedError("gfv.optim.Adam: amsgrad=True needs a third moment buffer (the maximum of exp_avg_sq) the "
+                                      "fused launch does not keep")
+        if maximize:
+            raise NotImplementedError("gfv.optim.Adam: maximize=True - the fused launch descends; negate the loss instead")
+        if differentiable:
+            raise NotImplementedError("gfv.optim.Adam: differentiable=True - the fused launch is not recorded by autograd")
+        weight_decay = check_weight_decay(weight_decay)
+        defaults = dict(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps),
+                        weight_decay=0 if weight_decay == 0 else weight_decay, amsgrad=False, maximize=False)
+        if decoupled_weight_decay:
+            defaults["decoupled_weight_decay"] = True
+        self._decoupled = bool(decoupled_weight_decay)
         super().__init__(params, defaults)
-        if len(self.param_groups) != 1:
-            raise NotImplementedError("gfv.optim.Adam: one parameter group (one flat buffer, one launch)")
-        ps = self.param_groups[0]["params"]
+        if len(self.param_groups) > MAX_GROUPS:
+            raise ValueError(f"gfv.optim.Adam: {len(self.param_groups)} parameter groups, at most {MAX_GROUPS}")
+        self._check_shared()
+        ps = [p for g in self.param_groups for p in g["params"]]
         if not ps or any((not p.is_cuda) or p.dtype != torch.float32 for p in ps):
             raise RuntimeError("gfv.optim.Adam: fp32 parameters on the GPU (HIP kernels only, no CPU fallback)")
         dev = ps[0].device
@@ -55,6 +69,9 @@ class Adam(torch.optim.Optimizer):
         # launches inside step().  Every parameter is a segment: one whose `.grad` is None has zeros in its slots (below), which
         # add nothing to the norm - torch leaves it out
         self._guard = GradGuard(self.G, dev, max_grad_norm, skip_nonfinite)
+        # parameter groups (gfv/groups.py): the tables exist from the first step that needs them
+        # _stepped: positions that have state - loaded with some, or moved by a step (torch has no state for the others)
+        self._pg, self._frozen_seen, self._stepped = None, None, set()
         self._hyper_host = None
         self._sync_hyper()
         L.status_mirror()   # the launch publishes the device status word (include/gfv.h gfv_status_mirror)
@@ -78,6 +95,42 @@ class Adam(torch.optim.Optimizer):
             t = float(self.adam_state[0]) if steps_done is None else float(steps_done)
             L.check(L.load().gfv_adam_state_init(self.adam_state.data_ptr(), float(g["betas"][0]), float(g["betas"][1]), t,
                                                  L.stream_ptr()), "adam_state_init")
+
+    # parameter groups ------------------------------------------------------------------------------------------------
+    def _check_shared(self):
+        g0 = self.param_groups[0]
+        for g in self.param_groups:
+            for k in ("amsgrad", "maximize"):
+                if g.get(k):
+                    raise NotImplementedError(f"gfv.optim.Adam: a parameter group with {k}=True")
+            if tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"]:
+                raise NotImplementedError("gfv.optim.Adam: parameter groups with their own betas or eps - the step record (bias "
+                                          "corrections, 1 - beta) is shared by all groups")
+
+    def _groups_in_use(self):
+        gs = self.param_groups
+        return len(gs) > 1 or float(gs[0]["weight_decay"]) != 0.0 or bool(gs[0].get("frozen", False))
+
+    def _sync_groups(self):
+        """The tables follow param_groups (a scheduler edits "lr"; "weight_decay" and "frozen" may be edited too) and the set of
+        parameters whose `.grad` is None this step: those must not move under a decay, as in torch - their runs point at the
+        reserved frozen row, rewritten in place when the set changes."""
+        self._check_shared()
+        vals = [(float(g["lr"]), check_weight_decay(g["weight_decay"]), bool(g.get("frozen", False))) for g in self.param_groups]
+        if all(fr for _, _, fr in vals):   # (checked before a table is touched)
+            raise ValueError("gfv.optim.Adam: every parameter group is frozen: nothing left to optimise")
+        owner = [k for k, g in enumerate(self.param_groups) for _ in g["params"]]   # group of every parameter, by position
+        if self._pg is None:
+            self._pg = ParamGroups(self.G, self._params[0].device, {str(i): k for i, k in enumerate(owner)}, vals, self._decoupled)
+        self._pg.sync(vals, self._decoupled)
+        frozen = tuple(fr for _, _, fr in vals)
+        if frozen != self._frozen_seen:
+            # the guard's norm covers what clip_grad_norm_ would see: no frozen group
+            self._guard.set_segments(self.G, {str(i) for i, k in enumerate(owner) if frozen[k]})
+            self._frozen_seen = frozen
+        none = {i for i, p in enumerate(self._params) if p.grad is None}
+        self._pg.set_rows(none)
+        self._stepped |= {i for i, k in enumerate(owner) if not frozen[k] and i not in none}
 
     def _flat_grad(self):
         """The gradients as ONE flat tensor in this object's layout.  NNmodel's backward returns exactly that - views of one
@@ -131,6 +184,13 @@ class Adam(torch.optim.Optimizer):
         g = self._flat_grad()
         if g is None:
             return loss
+        if self._pg is not None or self._groups_in_use():
+            self._sync_groups()
+            self._pg.launch(self._guard, None, None, self.flat_p, g, self.flat_m, self.flat_v, self.G.total, 1, None,
+                            self.adam_state, self.hyper)
+            return loss
+        if len(self._stepped) != len(self._params):
+            self._stepped = set(range(len(self._params)))   # (without groups every parameter takes part in the launch)
         if self._guard.active:
             self._guard.launch(self.flat_p, g, self.flat_m, self.flat_v, self.G.total, self.adam_state, self.hyper)
             return loss
@@ -161,18 +221,25 @@ class Adam(torch.optim.Optimizer):
         state = {}
         for i, (p, off) in enumerate(zip(self._params, self._offs)):
             k = p.numel()
+            if self._pg is not None and i not in self._stepped:
+                continue   # (frozen, or never with a gradient: no state in torch either)
             state[i] = {"step": t.clone(), "exp_avg": self.flat_m[off:off + k].view(p.shape).detach().cpu().clone(),
                         "exp_avg_sq": self.flat_v[off:off + k].view(p.shape).detach().cpu().clone()}
-        g = self.param_groups[0]
-        group = {k: v for k, v in g.items() if k != "params"}
-        group["params"] = list(range(len(self._params)))
-        return {"state": state, "param_groups": [group]}
+        groups, at = [], 0
+        for g in self.param_groups:
+            group = {k: v for k, v in g.items() if k != "params"}
+            group["params"] = list(range(at, at + len(g["params"])))
+            at += len(g["params"])
+            groups.append(group)
+        return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
-        g = sd["param_groups"][0]
-        if len(g["params"]) != len(self._params):
+        if [len(g["params"]) for g in sd["param_groups"]] != [len(g["params"]) for g in self.param_groups]:
             raise ValueError("optimizer state belongs to a different parameter set")
-        step = None
+        steps = {float(st["step"]) for st in sd["state"].values()}
+        if len(steps) > 1:   # (checked before a buffer is touched)
+            raise ValueError("per-parameter step counts differ: not a state this fused Adam can resume")
+        step = steps.pop() if steps else None
         self.flat_m.zero_()
         self.flat_v.zero_()
         for i, st in sd["state"].items():
@@ -180,14 +247,20 @@ class Adam(torch.optim.Optimizer):
             off, k = self._offs[i], self._params[i].numel()
             self.flat_m[off:off + k].copy_(st["exp_avg"].reshape(-1))
             self.flat_v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
-            s = float(st["step"])
-            step = s if step is None else step
-            if s != step:
-                raise ValueError("per-parameter step counts differ: not a state this fused Adam can resume")
-        for k, v in g.items():
-            if k != "params":
-                self.param_groups[0][k] = v
+        for mine, g in zip(self.param_groups, sd["param_groups"]):
+            for k, v in g.items():
+                if k != "params":
+                    mine[k] = v
+        self._stepped = {int(i) for i in sd["state"]}
         self._sync_hyper(steps_done=0.0 if step is None else step)
+
+
+class AdamW(Adam):
+    """torch.optim.AdamW on the fused launch: `Adam` with torch's AdamW defaults (weight_decay = 1e-2) and decoupled decay."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, **kw):
+        kw.pop("decoupled_weight_decay", None)
+        super().__init__(params, lr, betas, eps, weight_decay, amsgrad, decoupled_weight_decay=True, **kw)
 
 
 class LBFGS(torch.optim.Optimizer):

@@ -48,6 +48,7 @@ from . import cmdlist
 from . import lib as L
 from .accum import check_accum_steps
 from .ema import check_ema
+from .groups import check_groups
 from .guard import check_policy
 from .trainer import TrainStep
 
@@ -68,12 +69,14 @@ class PoolTrainStep(TrainStep):
 
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
-                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True):
+                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
+                 decoupled_weight_decay=True, param_groups=None):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
         check_accum_steps(accum_steps, bool(distributed))
         check_ema(ema_decay, ema_warmup)
+        check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
@@ -81,7 +84,8 @@ class PoolTrainStep(TrainStep):
         super().__init__(model, graphs, lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, world_size=1, use_graph=use_graph,
                          want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
                          skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
+                         decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = collections.OrderedDict()                    # key -> _Recorded, least recently used first

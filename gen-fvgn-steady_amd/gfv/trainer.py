@@ -20,6 +20,7 @@ from .accum import GradAccum, check_accum_steps
 from .ema import WeightEMA, check_ema
 from .engine import GradStore
 from .functions import unused_param_names
+from .groups import ParamGroups, check_groups, check_weight_decay
 from .guard import GradGuard, check_policy
 from .plan import _live_key, _refresh_live, get_plan
 
@@ -31,10 +32,12 @@ def _gather(src, index, out):
 class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
-                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True):
+                 skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
+                 decoupled_weight_decay=True, param_groups=None):
         check_policy(max_grad_norm, skip_on_flag, (world_size > 1) if distributed is None else bool(distributed))
         accum_steps = check_accum_steps(accum_steps, (world_size > 1) if distributed is None else bool(distributed))
         ema_decay = check_ema(ema_decay, ema_warmup)
+        spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -42,6 +45,7 @@ class TrainStep:
         self.engine = model.engine()
         p = model.params
         self._hyper_host = None
+        self._gs, self._pg, self._stateful = spec, None, None
         self._lr = p.lr if lr is None else lr
         self._betas, self._eps = tuple(betas), eps
         self._lw = tuple(loss_weights or (p.loss_cont, p.loss_mom, p.loss_press))
@@ -93,6 +97,11 @@ class TrainStep:
         # averaged weights (gfv/ema.py): None with ema_decay None - no third buffer, _adam() as it was
         self._ema_warmup = bool(ema_warmup)
         self._ema = WeightEMA(self.flat_p, total, ema_decay, self._ema_warmup) if ema_decay is not None else None
+        # parameter groups (gfv/groups.py): None with everything at its default - no table, _adam() as it was
+        self._graphs, self._list_warm = {}, {}
+        spec.skip = set(self.G.skip)
+        spec.check_some_live([g["frozen"] for g in spec.groups])
+        self._groups_changed(frozen_changed=bool(spec.frozen_names()))
         self.x = graphs[0].x
         self.x_backup = self.x.clone()
         B = self.plan.B
@@ -100,8 +109,6 @@ class TrainStep:
         self.gloss = torch.zeros((B, 4), dtype=torch.float32, device=dev)
         self.losses = None
         self.uvp_node = None
-        self._graphs = {}
-        self._list_warm = {}
 
     # hidden_size below 128 (FVMmodel/padding.py): parameters, moments and gradients of the TRUE shapes stay the state
     # (flat_p / flat_m / flat_v / flat_g, what Adam and the checkpoints see); every step gathers the parameters into the
@@ -141,6 +148,8 @@ class TrainStep:
             self._hyper_host = vals
             if betas_moved:
                 self._init_adam_state()
+        if self._pg is not None:
+            self._pg.sync(self._gs.values(self._lr), self._gs.decoupled)   # (every group's rate is lr * lr_scale)
 
     def _init_adam_state(self, steps_done=None):
         """The device-side bias corrections of the next step, from the step count (a new object, a loaded checkpoint, new betas)."""
@@ -204,6 +213,63 @@ class TrainStep:
     @skip_on_flag.setter
     def skip_on_flag(self, v):
         self._set_guard(skip_on_flag=v)
+
+    # parameter groups: per-group rate (lr * lr_scale), weight decay and freezing inside the Adam launch
+    def _groups_changed(self, frozen_changed=False):
+        gs = self._gs
+        if self._pg is None:
+            if gs.trivial:
+                return
+            self._pg = ParamGroups(self.G, self.dev, gs.group_of, gs.values(self._lr), gs.decoupled)
+            self._stateful = self._live_names()
+            self._graphs.clear()
+            self._list_warm.clear()
+        self._pg.sync(gs.values(self._lr), gs.decoupled)
+        if frozen_changed:
+            frozen = gs.frozen_names()
+            self._stateful |= self._live_names()
+            self._guard.set_segments(self.G, frozen)
+            self._graphs.clear()
+            self._list_warm.clear()
+
+    def _live_names(self):
+        """Parameters that move now: with a gradient and in no frozen group."""
+        frozen = self._gs.frozen_names()
+        return {n for n in self.G.off if n not in self.G.skip and n not in frozen}
+
+    @property
+    def param_groups(self):
+        """[{"params": names, "lr", "lr_scale", "weight_decay", "frozen"}] per group: the caller's groups in their order, then the
+        implicit default group of the parameters no group selected (lr_scale 1, the object's weight_decay, not frozen).  A group's
+        rate is `ts.lr * lr_scale`; its decay is decoupled (AdamW) or an L2 term (`decoupled_weight_decay=False`) for all groups
+        alike.  Read-only: change values with set_group().  betas, eps and the STEP COUNT are shared by all groups - see
+        set_group() for what that means for a group that is unfrozen later."""
+        return self._gs.public(self._lr)
+
+    def set_group(self, i, lr_scale=None, weight_decay=None, frozen=None):
+        """New values for group `i` of `param_groups` (None: unchanged); checked before anything changes.
+
+        A new lr_scale or weight_decay goes through the device table the Adam launch reads: recorded lists and captured graphs
+        follow it, nothing is recorded again.  A change of `frozen` also gives the guard a new segment table (its norm covers what
+        clip_grad_norm_ would see: no frozen group, no parameter without a gradient) and drops lists and graphs - a rare event,
+        like switching the guard on.  Freezing the last group that still moves raises ValueError.
+
+        A frozen group keeps its bits - parameters, moments, averaged weights - whatever the decay, and has no entry in
+        state_dict()["state"] until it has moved.  It is still differentiated by the backward (its gradient is computed, not used).
+
+        One deviation from torch.optim: the step count is shared.  torch counts steps per parameter, so a group unfrozen after k
+        steps starts its bias correction at 1 there; here its next step carries the shared count k + 1 with the moments it has
+        (zero if it never moved): a first update of 0.58 lr instead of lr at k = 3, up to 3.2 lr for large k, until the moments
+        have filled (about ten steps)."""
+        self._groups_changed(self._gs.set_group(int(i), lr_scale, weight_decay, frozen))
+
+    weight_decay = property(lambda self: self._gs.weight_decay)
+    decoupled_weight_decay = property(lambda self: self._gs.decoupled)
+
+    @weight_decay.setter
+    def weight_decay(self, v):
+        self._gs.weight_decay = check_weight_decay(v)
+        self._groups_changed()
 
     # gradient accumulation: `accum_steps` is an attribute like lr.  A new value is mirrored into the device record and drops the
     # open accumulation; only a change between 1 and more than 1 changes the launch sequence and drops lists and graphs.
@@ -340,13 +406,20 @@ class TrainStep:
         state = {}
         for i, n in enumerate(names):
             off, k = self.G.off[n], self.G.numel(n)
-            if n in self.G.skip:
-                continue   # parameters without a gradient have no Adam state in torch either
+            if n in self.G.skip or (self._stateful is not None and n not in self._stateful):
+                continue   # parameters without a gradient (or frozen since construction / load) have no Adam state in torch either
             state[i] = {"step": t.clone(), "exp_avg": self.flat_m[off:off + k].view(self.G.shape[n]).detach().cpu().clone(),
                         "exp_avg_sq": self.flat_v[off:off + k].view(self.G.shape[n]).detach().cpu().clone()}
         group = {"lr": self._lr, "betas": self._betas, "eps": self._eps, "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "params": list(range(len(names)))}
         sd = {"state": state, "param_groups": [group], "gfv_param_names": names, "gfv_loss_weights": self._lw}
+        if self._pg is not None:
+            # one entry per group in torch's nesting ("params": positions in model.parameters() order); a torch.optim.AdamW built
+            # with the same grouping loads it.  lr_scale, frozen: keys torch keeps and ignores
+            pos = {n: i for i, n in enumerate(names)}
+            sd["param_groups"] = [dict(group, lr=g["lr"], weight_decay=g["weight_decay"], lr_scale=g["lr_scale"], frozen=g["frozen"],
+                                       params=[pos[n] for n in g["params"]]) for g in self._gs.public(self._lr)]
+            sd["gfv_groups"] = {"lr": self._lr, "weight_decay": self._gs.weight_decay, "decoupled": self._gs.decoupled}
         if self._ema is not None:
             # (a top-level key torch.optim.Adam.load_state_dict ignores, as it does the two above)
             avg = self.ema_parameters()
@@ -359,7 +432,12 @@ class TrainStep:
         names = list(self.G.off)
         if "gfv_param_names" in sd and list(sd["gfv_param_names"]) != names:
             raise ValueError("optimizer state belongs to a different parameter set")
-        step = None
+        # everything is checked before a buffer or a group is touched
+        steps = {float(st["step"]) for st in sd["state"].values()}
+        if len(steps) > 1:
+            raise ValueError("per-parameter step counts differ: not a state this fused Adam can resume")
+        step = steps.pop() if steps else None
+        plan = self._plan_groups(sd, names)
         self.flat_m.zero_()
         self.flat_v.zero_()
         for i, st in sd["state"].items():
@@ -367,14 +445,28 @@ class TrainStep:
             off, k = self.G.off[n], self.G.numel(n)
             self.flat_m[off:off + k].copy_(st["exp_avg"].reshape(-1))
             self.flat_v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
-            step = float(st["step"]) if step is None else step
-            if float(st["step"]) != step:
-                raise ValueError("per-parameter step counts differ: not a state this fused Adam can resume")
         g = sd["param_groups"][0]
-        self._lr, self._betas, self._eps = float(g["lr"]), (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+        self._betas, self._eps = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
+        frozen_moved = False
+        if plan is None:
+            # a dict without groups (a pre-training checkpoint, torch.optim.Adam): an object without groups takes its rate, as it
+            # always did; a grouped object keeps its own rate and group values - the dict says nothing about them
+            if self._pg is None:
+                self._lr = float(g["lr"])
+        else:
+            gs = self._gs
+            self._lr, gs.weight_decay, gs.decoupled = plan["lr"], plan["weight_decay"], plan["decoupled"]
+            for i, (scale, wd, fr) in enumerate(plan["groups"]):
+                frozen_moved |= gs.set_group(i, scale, wd, None)
+                if fr is not None and fr != gs.groups[i]["frozen"]:
+                    gs.groups[i]["frozen"], frozen_moved = fr, True      # (checked as a whole in _plan_groups)
         if "gfv_loss_weights" in sd:
             self._lw = tuple(float(x) for x in sd["gfv_loss_weights"])
         self._sync_hyper()
+        self._groups_changed(frozen_moved)
+        if self._pg is not None:
+            # what has state: what the dict had state for, and what moves now (its moments are live from the next step on)
+            self._stateful = {names[int(i)] for i in sd["state"]} | self._live_names()
         self._init_adam_state(0.0 if step is None else step)
         self.accum_reset()
         if self._ema is not None:
@@ -387,6 +479,38 @@ class TrainStep:
                     self._ema.e[off:off + k].copy_(t.reshape(-1))
                 self._ema_warmup = bool(avg["warmup"])
                 self._ema.set(check_ema(avg["decay"]), self._ema_warmup, int(avg["updates"]))
+
+    def _plan_groups(self, sd, names):
+        """What a state_dict says about the groups, checked and nothing changed: None for a dict without groups (one group over
+        all parameters and no `gfv_groups` key: a pre-training checkpoint loads into a grouped fine-tuning object, which keeps its
+        own groups), else {"lr", "weight_decay", "decoupled", "groups": [(lr_scale, weight_decay, frozen)]} - for which the
+        grouping (which parameter is in which group) must be the one this object was built with."""
+        groups, gs = sd["param_groups"], self._gs
+        extra = sd.get("gfv_groups")
+        if len(groups) == 1 and extra is None and sorted(groups[0]["params"]) == list(range(len(names))):
+            return None
+        pos = {n: i for i, n in enumerate(names)}
+        if [list(g["params"]) for g in groups] != [[pos[n] for n in g["names"]] for g in gs.groups]:
+            raise ValueError("optimizer state belongs to a different parameter grouping")
+        if extra is not None:
+            lr, wd, dec = float(extra["lr"]), check_weight_decay(extra["weight_decay"]), bool(extra["decoupled"])
+        else:
+            # (a torch.optim.AdamW dict: the object's rate is the one its first group's lr_scale leads back to)
+            s0 = gs.groups[0]["lr_scale"]
+            lr = float(groups[0]["lr"]) / s0 if s0 > 0 else self._lr
+            wd, dec = gs.weight_decay, bool(groups[0].get("decoupled_weight_decay", gs.decoupled))
+        out = []
+        for g, mine in zip(groups, gs.groups):
+            scale = g.get("lr_scale")
+            if scale is None:
+                scale = float(g["lr"]) / lr if lr > 0 else mine["lr_scale"]
+            fr = g.get("frozen")
+            out.append((float(scale), check_weight_decay(g.get("weight_decay", wd)), None if fr is None else bool(fr)))
+        gs.check_some_live([mine["frozen"] if fr is None else fr for (_, _, fr), mine in zip(out, gs.groups)])
+        for scale, _, _ in out:
+            if not scale >= 0:
+                raise ValueError(f"lr_scale must be a finite number >= 0, got {scale!r}")
+        return {"lr": lr, "weight_decay": wd, "decoupled": dec, "groups": out}
 
     def named_state(self):
         """{name: (parameter, exp_avg, exp_avg_sq)} views of the flat buffers.  (The alignment padding between tensors is not
@@ -455,6 +579,11 @@ class TrainStep:
             self._adam()
 
     def _adam(self):
+        if self._pg is not None:
+            # the same one to three launches as below, the last of them the grouped Adam (gfv_adam_step_groups_dev)
+            self._pg.launch(self._guard, self._accum, self._ema, self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params,
+                            self.plan.B, self.loss, self.adam_state, self.hyper)
+            return
         if self._ema is not None:
             self._adam_ema()
             return

@@ -673,6 +673,38 @@ int gfv_adam_step_accum_dev(float* p, const float* g, float* m, float* v, int64_
 int gfv_ema_init(float* ema, float decay, int32_t warmup, int32_t updates, void* stream);
 int gfv_adam_step_ema_dev(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* state, const float* hyper,
                           const float* guard, const float* accum, float* ema, void* stream);
+/* Parameter groups: the Adam launch with a learning rate, a weight decay and a "leave this alone" per GROUP of
+ * parameter tensors - torch.optim.Adam / AdamW with param_groups - in the same single launch.  Everything that varies lies in two
+ * device tables, so a recorded list or a captured graph follows a change of value as it follows hyper[0]:
+ *   run table   one run per parameter tensor of the flat layout, in layout order.  run_start: n_runs + 1 int64, ascending,
+ *               run_start[0] = 0, run_start[n_runs] = n (a tensor's alignment padding belongs to its run); run_group: n_runs int32,
+ *               the row of each run in the group table, 0 .. GFV_MAX_PARAM_GROUPS (values outside are clamped).  n_runs is at most
+ *               GFV_MAX_PARAM_RUNS (the run starts are staged in LDS) and fixed for the life of the owner; membership changes
+ *               by rewriting run_group in place.
+ *   groups      (GFV_MAX_PARAM_GROUPS + 2) * 8 32-bit words.  Row 0 is the header {n_groups (int32), decoupled (int32), 0 ...}:
+ *               decoupled != 0 is AdamW's decay, 0 is Adam's L2 term - one flag of the optimiser, not of a group.  Row 1 + k is
+ *               group k: {lr, weight_decay, flags (int32: GFV_GROUP_FROZEN), 0 ...}.  The last row (k = GFV_MAX_PARAM_GROUPS) is
+ *               reserved: always frozen, whatever it holds - the group of every parameter without a gradient.
+ * Per element of a live run, with lr and wd of its group (hyper[0] is not read):
+ *       gi = g[i] * grad_scale (* guard[3] with a guard)         - first, as clip_grad_norm_ comes before step()
+ *       L2 (wd != 0):        gi = gi + wd * p[i]
+ *       decoupled (wd != 0): p[i] <- p[i] * (float)(1 - (double)lr * (double)wd)
+ *       then the statements of gfv_adam_step_dev with step_size = (float)((double)lr / bc1)
+ *   betas, eps, the step count and the bias corrections stay shared (state[16], hyper[1..4]).  An element of a frozen run is neither
+ *   read nor written: p, m, v and e keep their bits.  A group unfrozen after k steps continues with the SHARED count k + 1 and the
+ *   moments it has (zero if it never moved) - torch would start its bias correction at 1.
+ * guard, accum, e + ema: each NULL or given, with the meaning and the skip rules of gfv_adam_step_ema_dev (e and ema together).  With
+ * one live group, weight_decay 0, the results are those of the entry point of the same form bit for bit.  A thread finds its run
+ * by bisection over the run starts (staged in LDS), once per grid sweep and only when its element left the run.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer (guard, accum, e / ema apart), n < 1, n_runs < 1 or > GFV_MAX_PARAM_RUNS,
+ * e without ema or ema without e,
+ * e overlapping p.  The tables are not validated: the caller builds them (gfv/groups.py). */
+#define GFV_MAX_PARAM_GROUPS 32
+#define GFV_MAX_PARAM_RUNS 1024
+enum { GFV_GROUP_FROZEN = 1 };
+int gfv_adam_step_groups_dev(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* state, const float* hyper,
+                             const float* guard, const float* accum, float* ema, const int64_t* run_start,
+                             const int32_t* run_group, int32_t n_runs, const float* groups, void* stream);
 int gfv_train_loss(const float* losses, int32_t B, float w_cont, float w_mom, float w_press, float* loss, float* gloss,
                    void* stream);
 /* same, weights read from the device: hyper[5..7] = {w_cont, w_mom, w_press} of the buffer gfv_adam_step_dev takes */
