@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void slice_gw_kernel(const float* __restrict__
 //   g_fx_mid    = de-slice of g_raw by w
 //   g_x_mid, per-block partials of (dWs, dbs, dT): the slice-softmax adjoint from gw
 // = slice_gw, deslice, slice_gw (accumulate) and slice_softmax_bwd of the four-launch form, term for term in the same
-// order (the results are bit-identical, tests/test_kernels_gpu.py), without gw [N,8,32] ever leaving the registers:
+// order (the results are equal to rounding, tests/test_slice_gpu.py), without gw [N,8,32] ever leaving the registers:
 // 182 MB of traffic per Transolver block become 78 MB, four launches one.  The two slice tensors of the block's graph are
 // staged in LDS; the region is reused for the dWs product once every thread is through with them.
 struct SlicePostArgs {
