@@ -105,6 +105,7 @@ class FvmMesh(C.Structure):
 
 
 POOL_MAX_GRAPHS, POOL_MAX_ATTRS, POOL_ROW_HEAD = 64, 56, 8   # GFV_POOL_* of include/gfv.h
+EVAL_RECORD = 16   # GFV_EVAL_RECORD of include/gfv.h: floats per row of the table gfv_eval_collect fills
 POOL_COPY, POOL_ADD, POOL_ROWPTR, POOL_FILL = 0, 1, 2, 3
 
 
@@ -260,6 +261,9 @@ _SIGNATURES = {
     "gfv_sweep_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "gfv_eval_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                   C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "gfv_trans_mlp_fwd": (C.c_int, [C.POINTER(TransMlp), C.c_void_p]),
     "gfv_trans_mlp_bwd": (C.c_int, [C.POINTER(TransMlpBwd), C.c_void_p]),
     "gfv_trans_mlp_ln_rows": (C.c_int, [C.c_int32]),

@@ -961,6 +961,31 @@ int gfv_sweep_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
                       int32_t* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Evaluation over a device pool (gfv/evaluate.py; the training objective of pre_train_Adam.py:177-184 and field errors on
+ * entries that are not trained on).  ONE launch behind the forward-only step of a batch turns its outputs into a record of
+ * GFV_EVAL_RECORD floats per graph and writes it to row entry[b] of table [n_entries, GFV_EVAL_RECORD]:
+ *   columns 0-3    losses[b, 0:4] (cont, mom_x, mom_y, press), bit copies
+ *           4-6    || pred - cur ||_2 per channel u, v, p: pred = uvp_node, cur = x_raw[:, 0:3] (the entry's own state)
+ *           7-9    || pred ||_2 per channel
+ *           10-12  || pred - tgt ||_2 per channel, tgt = target3;  NaN for a graph with has_target[b] == 0
+ *           13-15  || tgt ||_2 per channel;                        NaN likewise
+ * over the nodes of graph b (chunk_beg / chunk_end / gchunk_ptr as for gfv_rollout_advance).  Nothing else is written: x_raw, the
+ * batch and the pool stay as they are.  entry and has_target are HOST arrays of B int32; they travel by value in the launch's
+ * argument block (as the indices of gfv_pool_assemble), so the launch is issued per batch and is not part of a recorded list.
+ * target3 [N, 3] is indexed like uvp_node and read only over the graphs that have a target; it may be NULL when none has.
+ * partial_ws: GFV_EVAL_RECORD - 4 doubles per chunk; counter: one int32, zero before the first launch and left at zero.
+ * Differences in fp32, squares and sums in double in the fixed order of gfv_rollout_advance, the square root in double, rounded
+ * to fp32: no floating-point atomics, results identical run to run.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer (target3: only with a target flag set), N, n_chunks, B or n_entries < 1,
+ * B > GFV_POOL_MAX_GRAPHS, an entry outside [0, n_entries), the same entry twice or an x_raw that is not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_EVAL_RECORD 16
+int gfv_eval_collect(const float* uvp_node, const float* x_raw, const float* target3, int32_t N, const int32_t* chunk_beg,
+                     const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* losses,
+                     const int32_t* entry, const int32_t* has_target, float* table, int32_t n_entries, double* partial_ws,
+                     int32_t* counter, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Pool training (gfv/pool.py BatchArena, gfv/pool_trainer.py; the changing-batch loop of pre_train_Adam.py:112-198 with
  * Data_Pool.payback, Graph_loader.py:370-396): a batch of ANY entries of the device-resident pool assembled into FIXED memory
  * by one launch, and the prediction written back by one launch.
