@@ -33,6 +33,16 @@ Normalizer.  As in the reference loop the model is called with `norm_global` eve
 `node_norm.should_accumulate()` exactly as `NNmodel.forward` does - for a trained model (accumulation count reached) that is
 "never".  A recorded list is made for ONE of the two values; when it flips (the count is reached during a rollout) the other
 list is warmed up and recorded.
+
+Anderson acceleration (`anderson=m`, 1 .. 8; gfv/anderson.py).  For the STEADY iteration: the rollout is the
+fixed-point iteration x_{k+1} = G(x_k), and with `anderson=m` two more launches between the forward and the advance mix the
+model's output with the last m residual differences per graph, decided on the device (nothing in them depends on the host: one
+recorded list serves every step).  `step()` then returns the iterate the rollout advanced to (uvp_node is overwritten in place;
+the losses and uvp_cell are the model's for the state it was given), history columns 4 / 5 hold the ACCELERATED update, and
+`run(tol=...)` tests the true fixed-point residual || G(x) - x || / || G(x) || of `anderson_history()` instead.  The accelerated
+iterates are not time steps of the model: a time-accurate unsteady rollout must leave it off.  The defaults
+`anderson_reg=1e-10` and `anderson_restart=10` are those of a CPU experiment on linear contractions; they have not been tuned on
+a trained model.  `anderson=0` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -40,6 +50,7 @@ import contextlib
 
 import torch
 
+from . import anderson as AA
 from . import cmdlist
 from . import lib as L
 from .functions import require_gpu
@@ -82,9 +93,11 @@ class WeightGuard:
 class Rollout:
     WARM = 2   # eager steps before a list is recorded (they are steps of the rollout like any other)
 
-    def __init__(self, model, graphs, max_steps=1000, launch_mode="cmd_list", norm_global=None):
+    def __init__(self, model, graphs, max_steps=1000, launch_mode="cmd_list", norm_global=None, anderson=0, anderson_beta=1.0,
+                 anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0):
         if launch_mode not in ("cmd_list", "eager"):
             raise ValueError('launch_mode must be "cmd_list" or "eager"')
+        aa_args = AA.check_args(anderson, anderson_beta, anderson_reg, anderson_restart, anderson_start)
         graph_node = graphs[0]
         x = graph_node.x
         require_gpu(x)
@@ -115,6 +128,8 @@ class Rollout:
         self._prep_ws = torch.zeros(max(lib.gfv_prep_workspace_bytes(pl.B) // 4, 1), dtype=torch.float32, device=dev)
         self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)
         L.status_mirror()
+        self.anderson = aa_args[0]
+        self._aa = AA.AndersonState(pl, dev, self.max_steps, *aa_args) if self.anderson else None
         self.steps_done = 0
         self._lists, self._warm = {}, {}
         self._outs = None
@@ -165,6 +180,8 @@ class Rollout:
                 self.P, self.buffers, self.x, pl, norm_global=self.norm_global, accumulate=acc, want_outputs=True,
                 want_edge_attr15=False, x_raw=self.x_backup, keep=False, static_weights=True)
         assert sv is None
+        if self._aa is not None:
+            self._aa.launch(uvp_node, self.x_backup, self._state)
         L.check(L.load().gfv_rollout_advance(
             uvp_node.data_ptr(), self.x_backup.data_ptr(), self.x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(),
             pl.chunk_end.data_ptr(), pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(),
@@ -174,7 +191,8 @@ class Rollout:
 
     def step(self):
         """One forward-only step + advance -> (losses [B,4], uvp_node [N,3], uvp_cell [C,3]).  In list mode the three are the
-        recorded step's own tensors: the next step overwrites them."""
+        recorded step's own tensors: the next step overwrites them.  With `anderson` > 0 uvp_node is the iterate the rollout
+        advanced to (the mixed one where the step was accelerated)."""
         L.raise_on_status("Rollout.step")
         check_room(self.steps_done, self.max_steps)
         self._guard.check()
@@ -206,15 +224,21 @@ class Rollout:
     def run(self, steps, tol=None, check_every=50):
         """`steps` steps -> the history so far as a CPU tensor [k, B, 6].  tol: stop early once every graph's relative update
         ||d uvp||_2 / ||uvp||_2 of the latest step is below it at a check - every `check_every` steps and after the last one;
-        a check is the only synchronisation (none at all without tol, until the history is copied out)."""
+        a check is the only synchronisation (none at all without tol, until the history is copied out).  With `anderson` > 0
+        the test is on the true fixed-point residual || G(x) - x ||_2 / || G(x) ||_2 of the latest step (`anderson_history()`
+        columns 0 / 1): history columns 4 / 5 then hold the accelerated update."""
         steps = int(steps)
         check_room(self.steps_done, self.max_steps, steps)
         check_every = max(1, int(check_every))
         for i in range(steps):
             self.step()
             if tol is not None and ((i + 1) % check_every == 0 or i + 1 == steps):
-                row = self.history[self.steps_done - 1].cpu()      # (synchronises)
-                rel = row[:, 4] / row[:, 5]
+                if self._aa is not None:
+                    row = self._aa.table[self.steps_done - 1].cpu()    # (synchronises)
+                    rel = row[:, 0] / row[:, 1]
+                else:
+                    row = self.history[self.steps_done - 1].cpu()      # (synchronises)
+                    rel = row[:, 4] / row[:, 5]
                 if bool((rel < tol).all()):
                     break
         return self.history[:self.steps_done].cpu()
@@ -230,5 +254,22 @@ class Rollout:
         self.x.copy_(src)
         self.history.zero_()
         self._state.zero_()
+        if self._aa is not None:
+            self._aa.reset()
         self.steps_done = 0
         self._outs = None
+
+    # ---- Anderson acceleration -----------------------------------------------------------------------------------------
+    def _need_anderson(self):
+        if self._aa is None:
+            raise RuntimeError("this Rollout was built with anderson=0")
+        return self._aa
+
+    def anderson_history(self):
+        """The acceleration's table so far as a CPU tensor [k, B, 4]: || G(x) - x ||_2, || G(x) ||_2, the depth used and the
+        flags (gfv.anderson.NONFINITE / GROWTH / SINGULAR) per step and graph."""
+        return self._need_anderson().table[:self.steps_done].cpu()
+
+    def anderson_stats(self):
+        """Restarts per graph (and the ring's state words); synchronises."""
+        return self._need_anderson().stats()

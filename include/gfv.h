@@ -986,6 +986,48 @@ int gfv_eval_collect(const float* uvp_node, const float* x_raw, const float* tar
                      int32_t* counter, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Anderson acceleration AA(m) of the steady-state rollout (gfv/anderson.py, gfv/rollout.py): two launches between
+ * the forward-only step and gfv_rollout_advance.  Per graph b over its node rows x 3 channels, fp32: x = x_backup[:, 0:3],
+ * g = uvp_node, f = g - x.  State of the caller's, zero before the first step and never touched by anything else:
+ *   f_prev, g_prev [N, 3] float;  dF, dG [m, N, 3] float (ring columns);  aa_state [B, 4] int32 (valid columns cnt, ring head,
+ *   has_prev, restarts);  r_prev [B] double (the last || f ||);  gamma [B, GFV_AA_MAX_DEPTH] double;  partial_ws
+ *   GFV_AA_PARTIALS * n_chunks doubles;  counter one int32 (left at zero);  aa_table [K_max, B, 4] float.
+ * gfv_anderson_gram: per row, with has_prev: dF[head] = f - f_prev, dG[head] = g - g_prev (fp32); then f_prev = f, g_prev = g.
+ *   Over the mk = min(cnt + has_prev, m) valid columns, the new one included, in double and in the fixed order of
+ *   gfv_rollout_advance (no floating-point atomics; a graph's sums do not depend on the rest of the batch): the upper triangle of
+ *   A = dF^T dF, dF^T f, || f ||^2, || g ||^2.  Then, per graph, with k = *step (the rollout's step counter, not written here), in
+ *   this order:
+ *     1. || f ||^2 not finite: restart - cnt = 0, has_prev = 0, flag GFV_AA_NONFINITE;
+ *     2. has_prev, restart > 0 and || f || > restart * r_prev: restart - cnt = 0 (the pair is kept), flag GFV_AA_GROWTH;
+ *     3. mk == 0 or k < start: depth 0 (the column is kept: cnt = mk, the head advances);
+ *     4. (A + reg * trace(A) / mk * I) gamma = dF^T f by Cholesky in double; a pivot <= 0 (an all-zero Gram matrix included) or a
+ *        gamma that is not finite: restart - cnt = 0, flag GFV_AA_SINGULAR;
+ *     5. otherwise depth = mk, cnt = mk, the head advances.
+ *   Every restart adds one to aa_state[b, 3].  gamma[b] is written in ring-slot order, zero for unused slots and whenever the
+ *   depth is 0; aa_table[k, b] = (|| f ||, || g ||, depth, flags).  With k outside [0, K_max) nothing is decided or mixed.
+ * gfv_anderson_mix: over the rows of every graph with depth > 0 (aa_table[k, b, 2]), in place,
+ *     uvp_node = g - (1 - beta) f - sum_j gamma_j (dG_j - (1 - beta) dF_j)
+ *   with f_cur = this step's f (what the gram launch left in f_prev), j in ascending ring slot over the slots with gamma_j != 0,
+ *   in double, rounded to fp32 once.  Rows of a graph with depth 0 are not written.  A row whose g never changes (dG = 0, f = 0)
+ *   keeps its bits.
+ * Both return GFV_ERR_ARG - before anything touches a device, nothing launched - on a NULL pointer, N, n_chunks, B or K_max < 1,
+ * m outside 1 .. GFV_AA_MAX_DEPTH, beta outside (0, 1], reg negative or NaN, restart negative, NaN or in (0, 1] (0 switches the
+ * growth test off), or a double buffer that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_AA_MAX_DEPTH 8
+#define GFV_AA_PARTIALS 46   /* 36 (upper triangle) + 8 (dF^T f) + || f ||^2 + || g ||^2 */
+#define GFV_AA_NONFINITE 1
+#define GFV_AA_GROWTH 2
+#define GFV_AA_SINGULAR 4
+int gfv_anderson_gram(const float* uvp_node, const float* x_backup, int32_t N, const int32_t* chunk_beg, const int32_t* chunk_end,
+                      const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, int32_t m, double reg, double restart, int32_t start,
+                      float* f_prev, float* g_prev, float* dF, float* dG, int32_t* aa_state, double* r_prev, double* gamma,
+                      double* partial_ws, int32_t* counter, float* aa_table, int32_t K_max, const int32_t* step, void* stream);
+int gfv_anderson_mix(float* uvp_node, const float* f_cur, int32_t N, const int32_t* chunk_beg, const int32_t* chunk_end,
+                     const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, int32_t m, double beta, const float* dF,
+                     const float* dG, const double* gamma, const float* aa_table, int32_t K_max, const int32_t* step, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Pool training (gfv/pool.py BatchArena, gfv/pool_trainer.py; the changing-batch loop of pre_train_Adam.py:112-198 with
  * Data_Pool.payback, Graph_loader.py:370-396): a batch of ANY entries of the device-resident pool assembled into FIXED memory
  * by one launch, and the prediction written back by one launch.
