@@ -854,49 +854,80 @@ extern "C" int gfv_adam_state_init(float* state, double beta1, double beta2, flo
   return GFV_OK;
 }
 
-extern "C" int gfv_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
-                                 void* stream) {
-  GfvProfScope ps_(GFV_K_MISC, 0, 28.0 * (double)n, stream);   // p, g, m, v in; p, m, v out
-  if (n <= 0) return GFV_OK;
-  if (!state || !hyper) return GFV_ERR_ARG;
-  int32_t* mirror = gfv_internal_status_mirror();
-  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
+// The one launcher behind the five gfv_adam_step*_dev entry points.  Each entry refuses what its own contract refuses and hands
+// the rest over; which kernel runs follows from the pointers that are given (include/gfv.h above gfv_adam_step_dev):
+// groups -> adam_groups_kernel<guard, accum, e>, else e -> adam_ema_kernel<guard, accum>, else adam_kernel<guard, accum>.
+namespace {
+struct AdamArgs {
+  float* p;
+  const float* g;
+  float *m, *v, *e;
+  int64_t n;
+  float* state;
+  const float *hyper, *guard, *accum;
+  float* ema;
+  const int64_t* run_start;
+  const int32_t* run_group;
+  int32_t n_runs;
+  const float* groups;
+};
+// run-time flags -> template arguments: f(std::bool_constant<flag>...) for the flags given
+template <bool... B, class F>
+void with_flags(F&& f) {
+  f(std::bool_constant<B>{}...);
+}
+template <bool... B, class F, class... Rest>
+void with_flags(F&& f, bool flag, Rest... rest) {
+  if (flag) with_flags<B..., true>(f, rest...);
+  else with_flags<B..., false>(f, rest...);
+}
+int adam_launch(const AdamArgs& a, void* stream) {
+  GfvProfScope ps_(GFV_K_MISC, 0, (a.e ? 36.0 : 28.0) * (double)a.n, stream);   // p, g, m, v (, e) in; p, m, v (, e) out
+  if (a.e && a.e < a.p + a.n && a.p < a.e + a.n) return GFV_ERR_ARG;   // (e == p among them: the average would be the iterate)
+  const int* status = gfv_internal_status_ptr();
+  int* mirror = gfv_internal_status_mirror();
+  long wgs = (a.n + ADAM_TPB - 1) / ADAM_TPB;
   if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  GFV_LAUNCH((adam_kernel<false, false>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-             (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr, (const float*)nullptr);
+  const dim3 grid((unsigned)wgs), block(ADAM_TPB);
+  const hipStream_t st = (hipStream_t)stream;
+  const long n = (long)a.n;
+  static_assert(sizeof(long) == sizeof(int64_t), "run table words");
+  with_flags([&](auto G, auto A, auto E) {
+    constexpr bool GUARDED = decltype(G)::value, ACCUM = decltype(A)::value, EMA = decltype(E)::value;
+    if (a.groups)
+      GFV_LAUNCH((adam_groups_kernel<GUARDED, ACCUM, EMA>), grid, block, 0, st, a.p, a.g, a.m, a.v, n, a.state, a.hyper, status, mirror,
+                 a.guard, a.accum, a.e, a.ema, reinterpret_cast<const long*>(a.run_start), (const int*)a.run_group, (int)a.n_runs,
+                 a.groups);
+    else if constexpr (EMA)
+      GFV_LAUNCH((adam_ema_kernel<GUARDED, ACCUM>), grid, block, 0, st, a.p, a.g, a.m, a.v, n, a.state, a.hyper, status, mirror, a.guard,
+                 a.accum, a.e, a.ema);
+    else
+      GFV_LAUNCH((adam_kernel<GUARDED, ACCUM>), grid, block, 0, st, a.p, a.g, a.m, a.v, n, a.state, a.hyper, status, mirror, a.guard,
+                 a.accum);
+  }, a.guard != nullptr, a.accum != nullptr, a.e != nullptr);
   GFV_CHECK_LAUNCH();
   return GFV_OK;
+}
+}  // namespace
+
+extern "C" int gfv_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
+                                 void* stream) {
+  if (n <= 0) return GFV_OK;
+  if (!state || !hyper) return GFV_ERR_ARG;
+  return adam_launch({p, g, m, v, nullptr, n, state, hyper, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr}, stream);
 }
 
 extern "C" int gfv_adam_step_guarded_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state,
                                          const float* hyper, const float* guard, void* stream) {
-  GfvProfScope ps_(GFV_K_MISC, 0, 28.0 * (double)n, stream);
   if (!p || !g || !m || !v || n <= 0 || !state || !hyper || !guard) return GFV_ERR_ARG;
-  int32_t* mirror = gfv_internal_status_mirror();
-  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
-  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  GFV_LAUNCH((adam_kernel<true, false>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-             (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, (const float*)nullptr);
-  GFV_CHECK_LAUNCH();
-  return GFV_OK;
+  return adam_launch({p, g, m, v, nullptr, n, state, hyper, guard, nullptr, nullptr, nullptr, nullptr, 0, nullptr}, stream);
 }
 
 // the Adam launch behind gfv_grad_accum_dev: guard == NULL is the plain step, else the guarded one; either obeys accum[3]
 extern "C" int gfv_adam_step_accum_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
                                        const float* guard, const float* accum, void* stream) {
-  GfvProfScope ps_(GFV_K_MISC, 0, 28.0 * (double)n, stream);
   if (!p || !g || !m || !v || n <= 0 || !state || !hyper || !accum) return GFV_ERR_ARG;
-  int32_t* mirror = gfv_internal_status_mirror();
-  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
-  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  if (guard)
-    GFV_LAUNCH((adam_kernel<true, true>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-               (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, accum);
-  else
-    GFV_LAUNCH((adam_kernel<false, true>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper,
-               (const int*)gfv_internal_status_ptr(), (int*)mirror, (const float*)nullptr, accum);
-  GFV_CHECK_LAUNCH();
-  return GFV_OK;
+  return adam_launch({p, g, m, v, nullptr, n, state, hyper, guard, accum, nullptr, nullptr, nullptr, 0, nullptr}, stream);
 }
 
 // Averaged weights (include/gfv.h): the record's four words, w by the one device statement of its formula
@@ -910,22 +941,8 @@ extern "C" int gfv_ema_init(float* ema, float decay, int32_t warmup, int32_t upd
 // the Adam launch of any of the three forms above (guard, accum: each NULL or given) that also advances the average e
 extern "C" int gfv_adam_step_ema_dev(float* p, const float* g, float* m, float* v, float* e, int64_t n, float* state,
                                      const float* hyper, const float* guard, const float* accum, float* ema, void* stream) {
-  GfvProfScope ps_(GFV_K_MISC, 0, 36.0 * (double)n, stream);   // p, g, m, v, e in; p, m, v, e out
   if (!p || !g || !m || !v || !e || n <= 0 || !state || !hyper || !ema) return GFV_ERR_ARG;
-  if (e < p + n && p < e + n) return GFV_ERR_ARG;   // (e == p among them: the average would be the iterate)
-  int32_t* mirror = gfv_internal_status_mirror();
-  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
-  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-#define GFV_ADAM_EMA(G, A)                                                                                                        \
-  GFV_LAUNCH((adam_ema_kernel<G, A>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, hyper, \
-             (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, accum, e, ema)
-  if (guard && accum) GFV_ADAM_EMA(true, true);
-  else if (guard) GFV_ADAM_EMA(true, false);
-  else if (accum) GFV_ADAM_EMA(false, true);
-  else GFV_ADAM_EMA(false, false);
-#undef GFV_ADAM_EMA
-  GFV_CHECK_LAUNCH();
-  return GFV_OK;
+  return adam_launch({p, g, m, v, e, n, state, hyper, guard, accum, ema, nullptr, nullptr, 0, nullptr}, stream);
 }
 
 // the Adam launch of any of the forms above (guard, accum, e + ema: each NULL or given) with per-group rate, decay and freezing
@@ -933,34 +950,10 @@ extern "C" int gfv_adam_step_groups_dev(float* p, const float* g, float* m, floa
                                         const float* hyper, const float* guard, const float* accum, float* ema,
                                         const int64_t* run_start, const int32_t* run_group, int32_t n_runs, const float* groups,
                                         void* stream) {
-  GfvProfScope ps_(GFV_K_MISC, 0, (e ? 36.0 : 28.0) * (double)n, stream);
   if (!p || !g || !m || !v || n <= 0 || !state || !hyper || !run_start || !run_group || n_runs < 1 ||
-      n_runs > GRP_LDS_RUNS || !groups)
+      n_runs > GRP_LDS_RUNS || !groups || (e == nullptr) != (ema == nullptr))
     return GFV_ERR_ARG;
-  if ((e == nullptr) != (ema == nullptr)) return GFV_ERR_ARG;
-  if (e && e < p + n && p < e + n) return GFV_ERR_ARG;
-  int32_t* mirror = gfv_internal_status_mirror();
-  long wgs = (n + ADAM_TPB - 1) / ADAM_TPB;
-  if (wgs > ADAM_MAX_WGS) wgs = ADAM_MAX_WGS;
-  static_assert(sizeof(long) == sizeof(int64_t), "run table words");
-#define GFV_ADAM_GROUPS(G, A, E)                                                                                                     \
-  GFV_LAUNCH((adam_groups_kernel<G, A, E>), dim3((unsigned)wgs), dim3(ADAM_TPB), 0, (hipStream_t)stream, p, g, m, v, (long)n, state, \
-             hyper, (const int*)gfv_internal_status_ptr(), (int*)mirror, guard, accum, e, ema,                                      \
-             reinterpret_cast<const long*>(run_start), (const int*)run_group, (int)n_runs, groups)
-  const int form = (guard ? 4 : 0) | (accum ? 2 : 0) | (e ? 1 : 0);
-  switch (form) {
-    case 0: GFV_ADAM_GROUPS(false, false, false); break;
-    case 1: GFV_ADAM_GROUPS(false, false, true); break;
-    case 2: GFV_ADAM_GROUPS(false, true, false); break;
-    case 3: GFV_ADAM_GROUPS(false, true, true); break;
-    case 4: GFV_ADAM_GROUPS(true, false, false); break;
-    case 5: GFV_ADAM_GROUPS(true, false, true); break;
-    case 6: GFV_ADAM_GROUPS(true, true, false); break;
-    default: GFV_ADAM_GROUPS(true, true, true); break;
-  }
-#undef GFV_ADAM_GROUPS
-  GFV_CHECK_LAUNCH();
-  return GFV_OK;
+  return adam_launch({p, g, m, v, e, n, state, hyper, guard, accum, ema, run_start, run_group, n_runs, groups}, stream);
 }
 
 extern "C" int gfv_grad_accum_dev(float* g, float* acc, int64_t n, int32_t B, const float* loss, float* accum, void* stream) {

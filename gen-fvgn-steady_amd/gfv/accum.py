@@ -1,16 +1,14 @@
 """Gradient accumulation: k micro-batches, one optimiser step, decided on the device (include/gfv.h gfv_grad_accum_dev,
-DESIGN.md 5g).  `GradAccum` owns the second flat gradient buffer `acc` and the device record `accum[8]`; `gfv.trainer.TrainStep`
-puts its three launches - accumulate, hold-aware norm (guard on), hold-aware Adam - where the one or two launches of `_adam()`
-were.  The same three launches are issued on every micro-step: which of them does what follows from the record's own count, so
-one recorded launch list or captured graph per batch signature serves the first, the middle and the closing micro-step alike.
-The host writes `steps` into word [0] and zeroes the open accumulation on a reset; it never tells a launch its phase."""
+DESIGN.md 5g).  `GradAccum` owns the second flat gradient buffer `acc` and the device record `accum[8]`; the launches that read
+them are issued by `gfv.optstep.optimizer_launches`, the same ones on every micro-step: which of them does what follows from the
+record's own count, so one recorded launch list or captured graph per batch signature serves the first, the middle and the
+closing micro-step alike.  The host writes `steps` into word [0] and zeroes the open accumulation on a reset; it never tells a
+launch its phase."""
 from __future__ import annotations
 
 import numbers
 
 import torch
-
-from . import lib as L
 
 
 def check_accum_steps(accum_steps, dist_on=False):
@@ -47,23 +45,6 @@ class GradAccum:
 
     def note_step(self):
         self.pending = (self.pending + 1) % self.steps
-
-    def launch(self, guard, p, g, m, v, n, B, loss, state, hyper, ema=None):
-        """The accumulate launch, the hold-aware norm + decision launch where the guard is active, the hold-aware Adam (ema: a
-        gfv.ema.WeightEMA - the hold-aware Adam that also advances the average on a closing micro-step)."""
-        lib, st = L.load(), L.stream_ptr()
-        rec = self.rec.data_ptr()
-        L.check(lib.gfv_grad_accum_dev(g.data_ptr(), self.acc.data_ptr(), n, int(B), loss.data_ptr(), rec, st), "grad_accum")
-        gptr = None
-        if guard is not None and guard.active:
-            gptr = guard.guard.data_ptr()
-            L.check(lib.gfv_grad_guard_accum_dev(g.data_ptr(), guard.segs.data_ptr(), guard.n_seg, guard.n_elems, hyper.data_ptr(),
-                                                 gptr, guard.ws.data_ptr(), rec, st), "grad_guard_accum")
-        if ema is not None:
-            ema.launch(p, g, m, v, n, state, hyper, guard=None if gptr is None else guard.guard, accum=self.rec)
-            return
-        L.check(lib.gfv_adam_step_accum_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, state.data_ptr(),
-                                            hyper.data_ptr(), gptr, rec, st), "adam_step_accum")
 
     def stats(self):
         """The device record (synchronises: for logging every so often)."""

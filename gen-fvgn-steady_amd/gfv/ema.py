@@ -1,9 +1,9 @@
 """Averaged weights: an exponential moving average of the parameters, advanced inside the fused Adam launch (include/gfv.h
-gfv_adam_step_ema_dev).  `WeightEMA` owns the flat average `e` and the device record `ema[8]`;
-`gfv.trainer.TrainStep` ends every branch of `_adam()` - plain, guarded, accumulating - in the one launch that also updates `e`.
-Whether an update happens is decided where the step is decided: a step the guard leaves out or a hold micro-step leaves `e`,
-the update count and the next weight as they were.  The host writes decay and warmup through `gfv_ema_init` (the weight's
-formula is evaluated on the device only); `ema_weight` below states the same formula for documentation and tests."""
+gfv_adam_step_ema_dev).  `WeightEMA` owns the flat average `e` and the device record `ema[8]`; the Adam launch
+that reads them is issued by `gfv.optstep.optimizer_launches`.  Whether an update happens is decided where the step is decided:
+a step that is left out or held back leaves `e`, the update count and the next weight as they were.  The host writes decay and
+warmup through `gfv_ema_init` (the weight's formula is evaluated on the device only); `ema_weight` below states the same formula
+for documentation and tests."""
 from __future__ import annotations
 
 import math
@@ -68,14 +68,6 @@ class WeightEMA:
             torch._foreach_copy_(list(tensors), avg)
             torch._foreach_copy_(avg, tmp)
         self.swapped = not self.swapped
-
-    def launch(self, p, g, m, v, n, state, hyper, guard=None, accum=None):
-        """The Adam launch of the plain (guard, accum None), guarded or accumulating step that also advances the average.
-        guard, accum: the device records (tensors) of the launches in front of it."""
-        L.check(L.load().gfv_adam_step_ema_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), self.e.data_ptr(), n,
-                                               state.data_ptr(), hyper.data_ptr(), None if guard is None else guard.data_ptr(),
-                                               None if accum is None else accum.data_ptr(), self.rec.data_ptr(), L.stream_ptr()),
-                "adam_step_ema")
 
     def stats(self):
         """The device record (synchronises: for logging every so often)."""

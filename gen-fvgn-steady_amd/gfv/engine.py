@@ -94,6 +94,10 @@ class GradStore:
             return None
         return self.flat[self.off[n]:self.off[n] + self.numel(n)].view(self.shape[n])
 
+    def view_of(self, buf, n):
+        """Tensor `n`, skipped or not, inside `buf`: any flat buffer of this layout (parameters, moments, an average)."""
+        return buf[self.off[n]:self.off[n] + self.numel(n)].view(self.shape[n])
+
     def block(self, first, last):
         """(offset, length) of the contiguous block first..last (inclusive, with padding)."""
         end = self.off[last] + (self.numel(last) + 3) // 4 * 4

@@ -4,8 +4,8 @@ inside the one Adam launch (include/gfv.h gfv_adam_step_groups_dev, DESIGN.md 5i
 Host side, most of it without a GPU: the selectors that say which parameter belongs to which group (`assign`), the checks every
 owner runs at construction (`check_groups` -> a `GroupSpec`), the run table of a flat layout (`build_runs`) and `ParamGroups`,
 the owner of the two device tables - run table and group table - which mirrors host values into them on change, as `_sync_hyper`
-does for `hyper`.  `gfv.trainer.TrainStep`, `gfv.pool_trainer.PoolTrainStep` and `gfv.optim.Adam` / `AdamW` put its launches
-where their Adam launch was once a group feature is in use; with everything at its default none of this is touched.
+does for `hyper`.  `gfv.trainer.TrainStep`, `gfv.pool_trainer.PoolTrainStep` and `gfv.optim.Adam` / `AdamW` hand it to
+`gfv.optstep.optimizer_launches` once a group feature is in use; with everything at its default none of this is touched.
 
 One deviation from torch: the step count is shared.  torch counts steps per parameter, so a group unfrozen after k steps starts
 its bias correction at 1 there; here it continues with the shared count k + 1 and the moments it has (zero if it never moved)."""
@@ -212,25 +212,3 @@ class ParamGroups:
         if rows != self._rows:
             self.run_group.copy_(torch.tensor(rows, dtype=torch.int32))
             self._rows = rows
-
-    def launch(self, guard, accum, ema, p, g, m, v, n, B, loss, state, hyper):
-        """The launches of one optimiser step in front of and including the grouped Adam: accumulate (accum: a gfv.accum.GradAccum
-        or None), norm + decision (guard: a gfv.guard.GradGuard, where active), Adam (ema: a gfv.ema.WeightEMA or None)."""
-        lib, st = L.load(), L.stream_ptr()
-        rec = None
-        if accum is not None:
-            rec = accum.rec.data_ptr()
-            L.check(lib.gfv_grad_accum_dev(g.data_ptr(), accum.acc.data_ptr(), n, int(B), loss.data_ptr(), rec, st), "grad_accum")
-        gptr = None
-        if guard is not None and guard.active:
-            gptr = guard.guard.data_ptr()
-            if rec is None:
-                L.check(lib.gfv_grad_guard_dev(g.data_ptr(), guard.segs.data_ptr(), guard.n_seg, guard.n_elems, hyper.data_ptr(),
-                                               gptr, guard.ws.data_ptr(), st), "grad_guard")
-            else:
-                L.check(lib.gfv_grad_guard_accum_dev(g.data_ptr(), guard.segs.data_ptr(), guard.n_seg, guard.n_elems,
-                                                     hyper.data_ptr(), gptr, guard.ws.data_ptr(), rec, st), "grad_guard_accum")
-        L.check(lib.gfv_adam_step_groups_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(),
-                                             None if ema is None else ema.e.data_ptr(), n, state.data_ptr(), hyper.data_ptr(), gptr,
-                                             rec, None if ema is None else ema.rec.data_ptr(), self.run_start.data_ptr(),
-                                             self.run_group.data_ptr(), self.n_runs, self.table.data_ptr(), st), "adam_step_groups")

@@ -1,8 +1,8 @@
 """Training guard: clip by global norm and leave bad steps out, decided on the device (include/gfv.h gfv_grad_guard_dev,
 DESIGN.md 5f).  `GradGuard` owns the device record `guard[8]`, the segment table of the gradient elements torch would see and
-the norm launch's workspace; `gfv.trainer.TrainStep` and `gfv.optim.Adam` put its two launches where their single Adam launch
-was.  The policy is three plain host values mirrored into `guard` on change (as `lr` is into `hyper`): nothing a recorded
-launch list or a captured graph holds depends on them."""
+the norm launch's workspace; the launches that read them are issued by `gfv.optstep.optimizer_launches`.  The policy is three
+plain host values mirrored into `guard` on change (as `lr` is into `hyper`): nothing a recorded launch list or a captured graph
+holds depends on them."""
 from __future__ import annotations
 
 import math
@@ -26,8 +26,8 @@ def check_policy(max_grad_norm, skip_on_flag=False, dist_on=False):
 
 def segments(store, exclude=()):
     """(offset, count) of every run of gradient elements of `store` (a gfv.engine.GradStore) that belongs to a used parameter:
-    no alignment padding, no parameter of `store.skip` or of `exclude` (the frozen parameter groups, gfv/groups.py: torch's
-    clip_grad_norm_ would not see them); neighbours without a gap are merged."""
+    no alignment padding, no parameter of `store.skip` or of `exclude` (frozen parameters: torch's clip_grad_norm_ would not see
+    them); neighbours without a gap are merged."""
     segs = []
     for n, off in store.off.items():
         k = store.numel(n)
@@ -72,18 +72,6 @@ class GradGuard:
             self.guard.view(torch.int32)[0:2].copy_(torch.tensor([bits, policy], dtype=torch.int32))
             self._host = vals
         self.active = policy != 0
-
-    def launch(self, p, g, m, v, n, state, hyper, ema=None):
-        """The norm + decision launch, then the Adam launch that obeys it (ema: a gfv.ema.WeightEMA - the Adam launch that also
-        advances the average, where the step is applied)."""
-        lib, st = L.load(), L.stream_ptr()
-        L.check(lib.gfv_grad_guard_dev(g.data_ptr(), self.segs.data_ptr(), self.n_seg, self.n_elems, hyper.data_ptr(),
-                                       self.guard.data_ptr(), self.ws.data_ptr(), st), "grad_guard")
-        if ema is not None:
-            ema.launch(p, g, m, v, n, state, hyper, guard=self.guard)
-            return
-        L.check(lib.gfv_adam_step_guarded_dev(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, state.data_ptr(),
-                                              hyper.data_ptr(), self.guard.data_ptr(), st), "adam_step_guarded")
 
     def stats(self):
         """What the last guarded step decided and the running counts (synchronises: for logging every so often)."""

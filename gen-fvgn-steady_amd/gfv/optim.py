@@ -25,6 +25,7 @@ from . import lib as L
 from .engine import GradStore
 from .groups import MAX_GROUPS, ParamGroups, check_weight_decay
 from .guard import GradGuard, check_policy
+from .optstep import optimizer_launches
 
 
 class Adam(torch.optim.Optimizer):
@@ -186,17 +187,10 @@ class Adam(torch.optim.Optimizer):
             return loss
         if self._pg is not None or self._groups_in_use():
             self._sync_groups()
-            self._pg.launch(self._guard, None, None, self.flat_p, g, self.flat_m, self.flat_v, self.G.total, 1, None,
-                            self.adam_state, self.hyper)
-            return loss
-        if len(self._stepped) != len(self._params):
+        elif len(self._stepped) != len(self._params):
             self._stepped = set(range(len(self._params)))   # (without groups every parameter takes part in the launch)
-        if self._guard.active:
-            self._guard.launch(self.flat_p, g, self.flat_m, self.flat_v, self.G.total, self.adam_state, self.hyper)
-            return loss
-        L.check(L.load().gfv_adam_step_dev(self.flat_p.data_ptr(), g.data_ptr(), self.flat_m.data_ptr(), self.flat_v.data_ptr(),
-                                           self.G.total, self.adam_state.data_ptr(), self.hyper.data_ptr(), L.stream_ptr()),
-                "adam_step")
+        optimizer_launches(self.flat_p, g, self.flat_m, self.flat_v, self.G.total, self.adam_state, self.hyper, guard=self._guard,
+                           groups=self._pg)
         return loss
 
     max_grad_norm = property(lambda self: self._guard.max_grad_norm)

@@ -22,6 +22,7 @@ from .engine import GradStore
 from .functions import unused_param_names
 from .groups import ParamGroups, check_groups, check_weight_decay
 from .guard import GradGuard, check_policy
+from .optstep import optimizer_launches
 from .plan import _live_key, _refresh_live, get_plan
 
 
@@ -34,8 +35,11 @@ class TrainStep:
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
                  decoupled_weight_decay=True, param_groups=None):
-        check_policy(max_grad_norm, skip_on_flag, (world_size > 1) if distributed is None else bool(distributed))
-        accum_steps = check_accum_steps(accum_steps, (world_size > 1) if distributed is None else bool(distributed))
+        # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
+        # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
+        dist_on = (world_size > 1) if distributed is None else bool(distributed)
+        check_policy(max_grad_norm, skip_on_flag, dist_on)
+        accum_steps = check_accum_steps(accum_steps, dist_on)
         ema_decay = check_ema(ema_decay, ema_warmup)
         spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         self.model = model
@@ -50,9 +54,7 @@ class TrainStep:
         self._betas, self._eps = tuple(betas), eps
         self._lw = tuple(loss_weights or (p.loss_cont, p.loss_mom, p.loss_press))
         self.world_size, self.pg = world_size, process_group
-        # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
-        # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
-        self.dist_on = (world_size > 1) if distributed is None else bool(distributed)
+        self.dist_on = dist_on
         self.engine.dist_world, self.engine.dist_group = world_size, process_group
         self.engine.dist_force = self.dist_on
         self.use_graph = use_graph
@@ -191,6 +193,11 @@ class TrainStep:
     skip_nonfinite = property(lambda self: self._guard.skip_nonfinite)
     skip_on_flag = property(lambda self: self._guard.skip_on_flag)
 
+    def _drop_recorded(self):
+        """Recorded lists and captured graphs hold the launch sequence and the addresses of the moment they were made."""
+        self._graphs.clear()
+        self._list_warm.clear()
+
     def _set_guard(self, **kw):
         g = self._guard
         new = dict(max_grad_norm=g.max_grad_norm, skip_nonfinite=g.skip_nonfinite, skip_on_flag=g.skip_on_flag)
@@ -199,8 +206,7 @@ class TrainStep:
         was = g.active
         g.set(**new)
         if g.active != was:
-            self._graphs.clear()
-            self._list_warm.clear()
+            self._drop_recorded()
 
     @max_grad_norm.setter
     def max_grad_norm(self, v):
@@ -222,15 +228,13 @@ class TrainStep:
                 return
             self._pg = ParamGroups(self.G, self.dev, gs.group_of, gs.values(self._lr), gs.decoupled)
             self._stateful = self._live_names()
-            self._graphs.clear()
-            self._list_warm.clear()
+            self._drop_recorded()
         self._pg.sync(gs.values(self._lr), gs.decoupled)
         if frozen_changed:
             frozen = gs.frozen_names()
             self._stateful |= self._live_names()
             self._guard.set_segments(self.G, frozen)
-            self._graphs.clear()
-            self._list_warm.clear()
+            self._drop_recorded()
 
     def _live_names(self):
         """Parameters that move now: with a gradient and in no frozen group."""
@@ -284,8 +288,7 @@ class TrainStep:
             return
         if (v > 1) != (self._accum is not None):
             self._accum = GradAccum(self.n_params, self.dev, v) if v > 1 else None
-            self._graphs.clear()
-            self._list_warm.clear()
+            self._drop_recorded()
         else:
             self._accum.set_steps(v)
 
@@ -322,8 +325,7 @@ class TrainStep:
         self._not_swapped("ema_decay")
         if (v is None) != (self._ema is None):
             self._ema = WeightEMA(self.flat_p, self.n_params, v, self._ema_warmup) if v is not None else None
-            self._graphs.clear()
-            self._list_warm.clear()
+            self._drop_recorded()
         else:
             self._ema.set(v, self._ema_warmup)
 
@@ -364,7 +366,7 @@ class TrainStep:
         """{name: CPU tensor} of the averaged weights, named and shaped as `model.param_names_tensors()` (no alignment padding)."""
         ema = self._need_ema("ema_parameters()")
         src = (self.flat_p if ema.swapped else ema.e).detach().cpu()
-        return {n: src[self.G.off[n]:self.G.off[n] + self.G.numel(n)].view(self.G.shape[n]).clone() for n in self.G.off}
+        return {n: self.G.view_of(src, n).clone() for n in self.G.off}
 
     @contextlib.contextmanager
     def ema_weights(self):
@@ -405,11 +407,10 @@ class TrainStep:
         t = self.adam_state[0:1].detach().cpu().clone().reshape(())
         state = {}
         for i, n in enumerate(names):
-            off, k = self.G.off[n], self.G.numel(n)
             if n in self.G.skip or (self._stateful is not None and n not in self._stateful):
                 continue   # parameters without a gradient (or frozen since construction / load) have no Adam state in torch either
-            state[i] = {"step": t.clone(), "exp_avg": self.flat_m[off:off + k].view(self.G.shape[n]).detach().cpu().clone(),
-                        "exp_avg_sq": self.flat_v[off:off + k].view(self.G.shape[n]).detach().cpu().clone()}
+            state[i] = {"step": t.clone(), "exp_avg": self.G.view_of(self.flat_m, n).detach().cpu().clone(),
+                        "exp_avg_sq": self.G.view_of(self.flat_v, n).detach().cpu().clone()}
         group = {"lr": self._lr, "betas": self._betas, "eps": self._eps, "weight_decay": 0, "amsgrad": False,
                  "maximize": False, "params": list(range(len(names)))}
         sd = {"state": state, "param_groups": [group], "gfv_param_names": names, "gfv_loss_weights": self._lw}
@@ -442,9 +443,8 @@ class TrainStep:
         self.flat_v.zero_()
         for i, st in sd["state"].items():
             n = names[int(i)]
-            off, k = self.G.off[n], self.G.numel(n)
-            self.flat_m[off:off + k].copy_(st["exp_avg"].reshape(-1))
-            self.flat_v[off:off + k].copy_(st["exp_avg_sq"].reshape(-1))
+            self.G.view_of(self.flat_m, n).copy_(st["exp_avg"].reshape(self.G.shape[n]))
+            self.G.view_of(self.flat_v, n).copy_(st["exp_avg_sq"].reshape(self.G.shape[n]))
         g = sd["param_groups"][0]
         self._betas, self._eps = (float(g["betas"][0]), float(g["betas"][1])), float(g["eps"])
         frozen_moved = False
@@ -475,8 +475,7 @@ class TrainStep:
             avg = sd.get("gfv_ema")
             if avg is not None:
                 for n, t in zip(names, avg["params"]):
-                    off, k = self.G.off[n], self.G.numel(n)
-                    self._ema.e[off:off + k].copy_(t.reshape(-1))
+                    self.G.view_of(self._ema.e, n).copy_(t.reshape(self.G.shape[n]))
                 self._ema_warmup = bool(avg["warmup"])
                 self._ema.set(check_ema(avg["decay"]), self._ema_warmup, int(avg["updates"]))
 
@@ -515,11 +514,7 @@ class TrainStep:
     def named_state(self):
         """{name: (parameter, exp_avg, exp_avg_sq)} views of the flat buffers.  (The alignment padding between tensors is not
         state: its gradient slots take whatever the shared slab workspace held, see gfv_dw_multi in include/gfv.h.)"""
-        out = {}
-        for n in self.G.off:
-            off, k, sh = self.G.off[n], self.G.numel(n), self.G.shape[n]
-            out[n] = tuple(b[off:off + k].view(sh) for b in (self.flat_p, self.flat_m, self.flat_v))
-        return out
+        return {n: tuple(self.G.view_of(b, n) for b in (self.flat_p, self.flat_m, self.flat_v)) for n in self.G.off}
 
     def advance_time(self):
         """Time advance of the reference's solve loop (solve_with_grad_GPU.py:180-197): after the inner iterations of a time
@@ -579,41 +574,9 @@ class TrainStep:
             self._adam()
 
     def _adam(self):
-        if self._pg is not None:
-            # the same one to three launches as below, the last of them the grouped Adam (gfv_adam_step_groups_dev)
-            self._pg.launch(self._guard, self._accum, self._ema, self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params,
-                            self.plan.B, self.loss, self.adam_state, self.hyper)
-            return
-        if self._ema is not None:
-            self._adam_ema()
-            return
-        if self._accum is not None:
-            # three launches, the same on every micro-step: fold this gradient into the accumulator (or, closing, the mean back
-            # into flat_g), then the norm (guard on) and the Adam that do nothing unless the first one closed the accumulation
-            self._accum.launch(self._guard, self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.plan.B,
-                               self.loss, self.adam_state, self.hyper)
-            return
-        if self._guard.active:
-            # two launches: the global norm of the gradient + the decision (clip coefficient, apply or not) into the device
-            # record, then the Adam that obeys it - no host decision, so lists and graphs replay it like any other launch
-            self._guard.launch(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper)
-            return
-        # ONE launch (round 6): its last workgroup advances the step count, forms the next step's bias corrections and publishes
-        # the device status word into the pinned mirror `step()` reads (include/gfv.h gfv_adam_step_dev, gfv_status_mirror)
-        L.check(L.load().gfv_adam_step_dev(self.flat_p.data_ptr(), self.flat_g.data_ptr(), self.flat_m.data_ptr(),
-                                           self.flat_v.data_ptr(), self.n_params, self.adam_state.data_ptr(),
-                                           self.hyper.data_ptr(), L.stream_ptr()), "adam_step")
-
-    def _adam_ema(self):
-        """The three branches of _adam() with the averaged weights on: the same launches in front, and in the place of each
-        branch's Adam launch the one that also advances the average (gfv_adam_step_ema_dev) - where the step is applied."""
-        args = (self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params)
-        if self._accum is not None:
-            self._accum.launch(self._guard, *args, self.plan.B, self.loss, self.adam_state, self.hyper, ema=self._ema)
-        elif self._guard.active:
-            self._guard.launch(*args, self.adam_state, self.hyper, ema=self._ema)
-        else:
-            self._ema.launch(*args, self.adam_state, self.hyper)
+        """The optimiser step's one to three launches (gfv/optstep.py): eager, list and hipGraph mode all go through here."""
+        optimizer_launches(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper,
+                           guard=self._guard, accum=self._accum, ema=self._ema, groups=self._pg, B=self.plan.B, loss=self.loss)
 
     # data-parallel exchange: the flat gradient is reduced in two buckets.  The upper one (last processor + decoder:
     # their backward runs first) goes out on a communication stream as soon as its last gradient kernel is launched and
@@ -686,8 +649,7 @@ class TrainStep:
         for n, t in self._probes:
             if t.data_ptr() != self.flat_p.data_ptr() + 4 * self.G.off[n]:
                 self.sync_from_model()
-                self._graphs.clear()
-                self._list_warm.clear()
+                self._drop_recorded()
                 return
 
     def step(self):
@@ -746,8 +708,7 @@ class TrainStep:
             if g is not None and g[1] != self.engine.capture_signature():
                 # the captured launches hold raw pointers into the weight-image set / descriptor tables of the engine:
                 # a changed set (model.to(), re-flattened parameters, a new weight block) makes every capture stale
-                self._graphs.clear()
-                self._list_warm.clear()   # (command lists were dropped with it: they re-record only after new warm-up steps)
+                self._drop_recorded()   # (command lists too: they re-record only after new warm-up steps)
                 g = None
             if g is None:
                 # warm the allocator on a side stream, then capture (PyTorch CUDA-graph recipe)
@@ -781,19 +742,16 @@ class TrainStep:
         return self.loss
 
     # state snapshot so the capture warm-up does not advance training ---------------------------------------
-    def _snapshot(self):
+    def _state_tensors(self):
         nb = self.model.node_norm
-        self._snap = (self.flat_p.clone(), self.flat_m.clone(), self.flat_v.clone(), self.adam_state.clone(), self._guard.guard.clone(),
-                      nb.acc_count.clone(), nb.num_accumulations.clone(), nb.acc_sum.clone(), nb.acc_sum_squared.clone())
-        if self._accum is not None:
-            self._snap += (self._accum.acc.clone(), self._accum.rec.clone())
-        if self._ema is not None:
-            self._snap += (self._ema.e.clone(), self._ema.rec.clone())
+        return ((self.flat_p, self.flat_m, self.flat_v, self.adam_state, self._guard.guard, nb.acc_count, nb.num_accumulations,
+                 nb.acc_sum, nb.acc_sum_squared)
+                + (() if self._accum is None else (self._accum.acc, self._accum.rec))
+                + (() if self._ema is None else (self._ema.e, self._ema.rec)))
+
+    def _snapshot(self):
+        self._snap = tuple(t.clone() for t in self._state_tensors())
 
     def _restore(self):
-        nb = self.model.node_norm
-        for dst, src in zip((self.flat_p, self.flat_m, self.flat_v, self.adam_state, self._guard.guard, nb.acc_count,
-                             nb.num_accumulations, nb.acc_sum, nb.acc_sum_squared)
-                            + (() if self._accum is None else (self._accum.acc, self._accum.rec))
-                            + (() if self._ema is None else (self._ema.e, self._ema.rec)), self._snap):
+        for dst, src in zip(self._state_tensors(), self._snap):
             dst.copy_(src)

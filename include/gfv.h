@@ -578,7 +578,13 @@ int gfv_prep_apply(const float* x_raw, float* x_out, const int32_t* batch, const
  *              launch in front, gfv_adam_tick_dev / gfv_adam_update_dev: removed)
  *   hyper[8] = {lr, beta1, beta2, eps, grad_scale (1 / world size), w_cont, w_mom, w_press}  (beta1 / beta2 here: the fp32 factors
  *              of the moment decay, as torch's fp32 kernels take them)
- * The same launch publishes the status word once gfv_status_mirror has been called. */
+ * The same launch publishes the status word once gfv_status_mirror has been called.
+ *
+ * The five entries gfv_adam_step_dev, _guarded_dev, _accum_dev, _ema_dev and _groups_dev (below) share one launcher: each refuses
+ * what its own contract says, the rest - grid, the e / p overlap refusal, the status word - is common.  Which kernel runs follows
+ * from the pointers given: groups -> the grouped kernel <guard, accum, e>; else e -> the averaging kernel <guard, accum>; else
+ * the plain kernel <guard, accum>, each template flag being "this pointer is not NULL".  So a form reached through a wider entry
+ * with its optional pointers NULL runs the same element statements as the narrower entry (the launch sequence). */
 int gfv_adam_state_init(float* state, double beta1, double beta2, float steps_done, void* stream);
 int gfv_adam_step_dev(float* p, const float* g, float* m, float* v, int64_t n, float* state, const float* hyper,
                       void* stream);
