@@ -17,27 +17,22 @@ batch of a `BatchArena` with one launch behind it (`gfv_eval_collect`, csrc/eval
 The pool is NOT written: no payback, no advance - every entry's `x` is bit for bit what it was.
 
 Per batch: `arena.load(batch)`; the targets of its entries copied into the staging buffer at the host-known node offsets; the
-body - `Sweep._body` without the advance: `Engine.forward(keep=False, static_weights=True)` - eager, recorded or replayed; then
+body - `Sweep._body` without the advance: `StaticForward.forward` and nothing behind it - eager, recorded or replayed; then
 `gfv_eval_collect`, which writes a 16-float record per graph into row `entry` of a device table `[n_entries, 16]` (the layout is in
 include/gfv.h).  The entry indices and the target flags travel by value in that launch's argument block, so it is issued eagerly
 behind the body and is not part of the recorded list: one list serves every batch of a size signature.
 
-Recorded lists are kept per ordered batch signature as in `Sweep`: two eager warm-ups, then record, then replay; bounded by
-`max_list_bytes`, least recently used out, `Sweep`'s eviction rule.  Warm-up counts and lists live across `run()` calls: the second
-epoch's evaluation replays.
+Recorded lists are kept per ordered batch signature in a `gfv.listcache.ListCache` bounded by `max_list_bytes`.  Warm-up counts
+and lists live across `run()` calls: the second epoch's evaluation replays.  A list the byte budget refuses is parked until the
+collect launch behind its body has been issued: its private pool holds the outputs that launch reads.
 
-Who owns what a recorded list points at.  (1) The list's private memory pool: activations and outputs.  (2) The arena (this
-object's own, or a shared one of the same pool - `PoolTrainStep.arena`: it is assembled afresh for every batch by whoever uses it):
-the plan, `x`, `x_raw`.  (3) This object, for its lifetime, never reallocated: the engine scratch of the input preparation and of
-the finite-volume tail, swapped into the engine for the duration of a body (`Sweep._own_scratch`'s rule and assertion), and the
-padded parameters of a narrow model.  (4) The engine's static weight-image set.  The table, the partial sums, the arrival counter
-and the target staging buffer `[capacity n, 3]` are this object's too and are read and written by the collect launch only.
+Who owns what a recorded list points at: DESIGN.md 5l.  The arena may be this object's own or a shared one of the same pool
+(`PoolTrainStep.arena`: it is assembled afresh for every batch by whoever uses it).  The table, the partial sums, the arrival
+counter and the target staging buffer `[capacity n, 3]` are this object's and are read and written by the collect launch only.
 
-`refresh_weights()` rebuilds the maximum and the forward weight images IN PLACE - same image memory, new contents - and refreshes
-a narrow model's padded copies with `copy_` into the tensors that exist, so that a recorded list stays valid: the lists are kept
-whenever the engine signature (`Sweep._engine_signature`) and the addresses of the parameters and Normalizer buffers are what they
-were before, and dropped otherwise (parameters that moved: `.to()`, another parameter set through the same engine, another product
-form).  The rebuild runs on the calling stream, behind every replay issued before it.
+`refresh_weights()` rebuilds the weight images and a narrow model's padded copies IN PLACE (gfv/static_forward.py), on the
+calling stream, behind every replay issued before it - so a recorded list stays valid: the lists are dropped only when something
+they point at moved (`.to()`, another parameter set through the same engine, another product form).
 """
 from __future__ import annotations
 
@@ -47,12 +42,11 @@ import math
 
 import torch
 
-from . import cmdlist
 from . import lib as L
+from . import listcache
 from .functions import require_gpu
 from .pool import batch_totals, check_fits
-from .rollout import WeightGuard
-from .sweep import Sweep, _Recorded
+from .static_forward import StaticForward, check_normalizer
 
 EvalReport = collections.namedtuple("EvalReport", "entries losses loss_batch objective rel_update rel_error nonfinite table")
 
@@ -105,8 +99,7 @@ def make_report(entries, table, loss_weights):
 
 
 class Evaluate:
-    WARM = Sweep.WARM
-    EVICT_MAX = Sweep.EVICT_MAX
+    WARM, EVICT_MAX = listcache.WARM, listcache.EVICT_MAX
 
     def __init__(self, model, pool, max_graphs=8, loss_weights=None, launch_mode="cmd_list", max_list_bytes=16 << 30,
                  max_sizes=None, arena=None):
@@ -119,7 +112,7 @@ class Evaluate:
         self.model, self.pool = model, pool
         p = model.params
         self.loss_weights = tuple(float(w) for w in (loss_weights or (p.loss_cont, p.loss_mom, p.loss_press)))
-        self._check_normalizer()
+        check_normalizer(model)
         require_gpu(pool.x[0])
         if arena is not None and arena.pool is not pool:
             raise ValueError("Evaluate: the arena belongs to another pool")
@@ -128,70 +121,29 @@ class Evaluate:
         dev = self.dev = pool.device
         cap, B = self.arena.capacity, self.arena.max_graphs
         self.norm_global = True        # (what the graphs of a pool carry: gfv.pool.BatchArena._make_views)
-        lib = L.load()
         # created once, never reallocated
         self.n_entries = pool.n
         self._table = torch.full((pool.n, L.EVAL_RECORD), float("nan"), dtype=torch.float32, device=dev)
         self._partial = torch.zeros((max(cap["nchunk"], 1), L.EVAL_RECORD - 4), dtype=torch.float64, device=dev)
         self._counter = torch.zeros(1, dtype=torch.int32, device=dev)
         self._target3 = torch.zeros((max(cap["n"], 1), 3), dtype=torch.float32, device=dev)
-        self._prep_ws = torch.zeros(max(lib.gfv_prep_workspace_bytes(B) // 4, 1), dtype=torch.float32, device=dev)
-        self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)
         L.status_mirror()
         self._targets = {}                           # entry -> [n_i, 3] fp32 on the device
-        self._lists = collections.OrderedDict()      # batch signature -> _Recorded (its outputs in cl.keep), least recently used first
-        self._warm, self._oversize, self._evicted = {}, set(), {}
-        self._counts = dict(batches=0, replayed=0, recorded=0, eager=0)
-        self._padded = {}                            # name -> padded copy of a narrow model's parameter
-        self._guard = WeightGuard(model)
-        self._sig = None
-        self.refresh_weights()
+        self._lists = listcache.ListCache(self.max_list_bytes, dev=dev)      # batch signature -> the recorded body
+        self._batches = 0
+        self._fwd = StaticForward(model, B, dev)
 
-    # ---- guards, weights -----------------------------------------------------------------------------------------------
-    _check_normalizer = Sweep._check_normalizer      # (Sweep's rule and message)
-    _engine_signature = Sweep._engine_signature
-    _own_scratch = Sweep._own_scratch
-
-    def _list_signature(self):
-        """What a recorded list points at outside its own pool, the arena and this object's scratch: the engine's image set
-        (Sweep._engine_signature) and the addresses of the parameters (a narrow model: of their padded copies) and buffers."""
-        return (self._engine_signature(), tuple(t.data_ptr() for t in self.P.values()),
-                tuple(b.data_ptr() for b in self.buffers.values()))
-
+    # ---- weights -------------------------------------------------------------------------------------------------------
     def refresh_weights(self):
-        """(Re)build what depends on the parameter VALUES, in place: padded copies (hidden_size < 128) by `copy_` into the tensors
-        that exist, the maximum and every forward weight image into the memory they have.  The recorded lists are kept when
-        nothing they point at moved, dropped otherwise."""
-        from FVMmodel.padding import pad_parameters
-        names, tensors = self.model.param_names_tensors()
-        P = {}
-        with torch.no_grad():
-            for name, src, t in zip(names, tensors, pad_parameters(names, tensors, self.model.hidden_size)):
-                if t is src:
-                    P[name] = src.detach()
-                    continue
-                own = self._padded.get(name)
-                if own is not None and own.shape == t.shape and own.device == t.device:
-                    own.copy_(t)
-                else:
-                    own = self._padded[name] = t.detach()
-                P[name] = own
-        self.P = P
-        self.buffers = self.model.node_norm.buffers_dict()
-        self.model.node_norm._host_num_acc = None
-        with self.engine.model_width():
-            # (same parameter set - same addresses: the maximum and EVERY known image are rebuilt where they are; another one:
-            # the engine starts a new image set, and the signature below says so)
-            self.engine.build_static_images(P)
-        self._guard.refresh()
-        sig = self._list_signature()
-        if sig != self._sig:
+        """(Re)build what depends on the parameter VALUES, in place.  The recorded lists are kept when nothing they point at
+        moved, dropped otherwise."""
+        if self._fwd.refresh():
             self._lists.clear()
-            self._warm = {}
-        self._sig = sig
+
+    P = property(lambda self: self._fwd.P)
 
     def stats(self):
-        return dict(self._counts, lists=len(self._lists), list_bytes=sum(e.bytes for e in self._lists.values()))
+        return dict(self._lists.stats(), batches=self._batches)
 
     # ---- targets -------------------------------------------------------------------------------------------------------
     def set_target(self, i, uvp):
@@ -210,47 +162,14 @@ class Evaluate:
 
     # ---- one batch -----------------------------------------------------------------------------------------------------
     def _body(self, graphs, pl):
-        x, x_raw = graphs[0].x, graphs[0]._gfv_x_raw
-        with self._own_scratch(), self.engine.model_width():
-            losses, uvp_node, _, _, sv = self.engine.forward(
-                self.P, self.buffers, x, pl, norm_global=self.norm_global, accumulate=False, want_outputs=True,
-                want_edge_attr15=False, x_raw=x_raw, keep=False, static_weights=True)
-        assert sv is None
+        losses, uvp_node, _ = self._fwd.forward(graphs[0].x, graphs[0]._gfv_x_raw, pl, False, self.norm_global)
         L.status_publish()
         return losses, uvp_node
 
     def _step(self, key, graphs, pl):
         """The body over the batch the arena holds, on the launch path of its signature -> (losses [B,4], uvp_node [N,3])."""
-        self._counts["batches"] += 1
-        listed = self.launch_mode == "cmd_list" and self.max_list_bytes > 0 and key not in self._oversize
-        ent = self._lists.get(key) if listed else None
-        if ent is not None:
-            self._lists.move_to_end(key)
-            ent.cl.replay()
-            self._counts["replayed"] += 1
-            return ent.cl.keep[0]
-        if not listed or self._warm.get(key, 0) < Evaluate.WARM:
-            if listed:
-                self._warm[key] = self._warm.get(key, 0) + 1
-            self._counts["eager"] += 1
-            return self._body(graphs, pl)
-        before = torch.cuda.memory_reserved(self.dev)
-        with cmdlist.record() as cl:
-            outs = self._body(graphs, pl)
-            cl.keep.append(outs)
-        nbytes = max(torch.cuda.memory_reserved(self.dev) - before, 0)      # the segments of the list's private pool
-        self._counts["recorded"] += 1
-        if nbytes > self.max_list_bytes:
-            self._oversize.add(key)
-            self._dropped = cl          # (its pool holds `outs` until the collect launch behind this body has been issued)
-            return outs
-        self._lists[key] = _Recorded(cl, nbytes)
-        while sum(e.bytes for e in self._lists.values()) > self.max_list_bytes and len(self._lists) > 1:
-            old, _ = self._lists.popitem(last=False)
-            self._evicted[old] = self._evicted.get(old, 0) + 1
-            if self._evicted[old] >= Evaluate.EVICT_MAX:
-                self._oversize.add(old)
-        return outs
+        self._batches += 1
+        return self._lists.run(key, lambda: self._body(graphs, pl), self.launch_mode == "cmd_list")
 
     def _collect(self, batch, pl, x_raw, losses, uvp_node):
         """Targets into the staging buffer (device-to-device, at the host-known node offsets), then the collect launch."""
@@ -277,20 +196,16 @@ class Evaluate:
         in the order asked.  One synchronisation, at the end.  The pool is not written."""
         L.raise_on_status("Evaluate.run")
         idx = check_indices(indices, min(self.pool.n, self.n_entries))
-        self._check_normalizer()
-        self._guard.check()
-        if self._list_signature() != self._sig:
-            raise RuntimeError("Evaluate: the engine's weight-image set changed under the evaluation (another parameter set or "
-                               "product form went through the same engine); call refresh_weights()")
+        check_normalizer(self.model)
+        self._fwd.check("Evaluate", "evaluation")
         batches = split_batches(idx, self.max_graphs)
         for batch in batches:           # every batch has to fit before anything is launched
             check_fits(batch_totals(self.pool.sizes, batch), len(batch), self.arena.capacity, self.arena.max_graphs)
-        self._dropped = None
         for batch in batches:
             graphs, pl = self.arena.load(batch)
             losses, uvp_node = self._step(self.arena.signature(batch), graphs, pl)
             self._collect(batch, pl, graphs[0]._gfv_x_raw, losses, uvp_node)
+            self._lists.parked = None   # (a list the byte budget refused: its pool held the outputs up to here)
         table = self._table.cpu()[idx]  # (the one synchronisation)
-        self._dropped = None
         L.raise_on_status("Evaluate.run")
         return make_report(idx, table, self.loss_weights)

@@ -14,58 +14,47 @@ Why a list recorded for one batch is valid for another.  A recorded list holds p
 batch is assembled into the SAME memory (`gfv.pool.BatchArena`, one launch of gfv_pool_assemble), so every batch with the same
 ordered size signature (per mesh: nodes, faces, cells, incidences, stencil entries, slice chunks) issues exactly the launches
 that were recorded - no host-side decision of `Engine.forward / backward` reads table CONTENTS, only sizes, limits and flags
-(DESIGN.md 5c).  Lists are kept per (signature, accumulate, distributed): the third step of a key records (two eager warm-up
-steps first, as `TrainStep` does), later ones replay; the cache is bounded by the bytes of the lists' private memory pools,
-least recently used out (a key evicted EVICT_MAX times stays eager: it would otherwise record on every visit).  The recorded list contains only the step; assembly and payback are issued around the replay.
+(DESIGN.md 5c).  Lists are kept per (signature, accumulate, distributed) in a `gfv.listcache.ListCache` bounded by
+`max_list_bytes`.  The recorded list contains only the step; assembly and payback are issued around the replay.
 
 Gradient accumulation (`accum_steps=k`, gfv/accum.py): k consecutive `step()` calls are one optimiser step over the
 mean gradient of all their graphs.  The key of a list is unchanged: the launches behind the backward are the same on every
 micro-step and read their phase from a device record, so the list of a signature is replayed in every phase.  With micro-batches
 of one or two meshes a pool of N sizes has N or N^2 ordered signatures instead of N^8, and every list is small.
 
-Who owns what a recorded list points at.  (1) The list's own private memory pool: activations and outputs.  (2) The arena: every
-plan tensor, the normalised `x` and the un-normalised state the input preparation reads (`x_raw=`).  (3) The flat parameter /
-gradient / moment buffers, `loss`, the per-B `gloss`, the Adam state: this object, for its lifetime.  (4) The engine's
-weight-image set (checked through `Engine.capture_signature()`).  (5) Engine scratch - `_zero_e`, `_dw_ws`, `_dw_ws_main`,
-`_prep_ws`, `_fvm_cnt` - owned by THIS object and swapped into the engine for the duration of a step (as `Rollout._own_scratch`
-does), so that another batch run through the same engine by someone else cannot replace it under a list.  `_prep_ws`,
-`_fvm_cnt` and `_zero_e` (one capacity-sized buffer viewed to E rows) are sized once for the arena's capacity and must not be
+Who owns what a recorded list points at: DESIGN.md 5l.  Particular to this object, for its lifetime: the flat parameter /
+gradient / moment buffers, `loss`, the per-B `gloss`, the Adam state.  The weight-image set is checked through
+`Engine.capture_signature()`.  The engine scratch of a training step - `_zero_e`, `_dw_ws`, `_dw_ws_main`, `_prep_ws`,
+`_fvm_cnt` - is owned by THIS object and swapped into the engine for the duration of a step.  `_prep_ws`, `_fvm_cnt` and `_zero_e` (one capacity-sized buffer viewed to E rows) are sized once for the arena's capacity and must not be
 re-allocated inside a step (asserted).  The two weight-gradient workspaces follow the engine's own grow-only rule - they are
 allocated and, for a batch larger than any before, re-allocated INSIDE a step by the engine, on exactly the steps where a plain
 `TrainStep` over the same batches would do it (the padding slots of the flat gradient take whatever that workspace held, so its
 history is part of the bit-identity with the eager path) - and when that happens the new tensor is adopted and EVERY list is
-dropped (the old tensor dies with them; the keys keep their warm-up counts and record again on their next visit).  Before a replay the engine signature and the pointers of all five pieces are compared with what the list was recorded
-against; on any mismatch the list is dropped and the step runs eager.  A stale list is never issued.
+dropped (the old tensor dies with them; the keys keep their warm-up counts and record again on their next visit).  Before a
+replay the engine signature and the pointers of all five pieces are compared with what the list was recorded against; on any mismatch the list is dropped and the step runs eager.  A stale list is never issued.
 """
 from __future__ import annotations
 
-import collections
 import contextlib
 
 import torch
 
 from . import cmdlist
 from . import lib as L
+from . import listcache
 from .accum import check_accum_steps
 from .ema import check_ema
 from .groups import check_groups
 from .guard import check_policy
+from .static_forward import prep_scratch
 from .trainer import TrainStep
 
 _SCRATCH = ("_zero_e", "_dw_ws", "_dw_ws_main", "_prep_ws", "_fvm_cnt")
 _FIXED = ("_zero_e", "_prep_ws", "_fvm_cnt")       # sized once for the arena's capacity
 
 
-class _Recorded:
-    __slots__ = ("cl", "engine_sig", "early", "scratch", "bytes", "outs")
-
-    def __init__(self, cl, engine_sig, early, scratch, nbytes, outs):
-        self.cl, self.engine_sig, self.early, self.scratch, self.bytes, self.outs = cl, engine_sig, early, scratch, nbytes, outs
-
-
 class PoolTrainStep(TrainStep):
-    WARM = 2   # eager steps of a key before its list is recorded (they are training steps like any other)
-    EVICT_MAX = 2
+    WARM, EVICT_MAX = listcache.WARM, listcache.EVICT_MAX
 
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
@@ -88,23 +77,17 @@ class PoolTrainStep(TrainStep):
                          decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
-        self._graphs = collections.OrderedDict()                    # key -> _Recorded, least recently used first
-        self._list_warm = {}
-        self._oversize = set()                                      # keys the byte budget has no room for: eager for good
-        self._evicted = {}
-        self._counts = dict(replayed=0, recorded=0, eager=0)
+        self._graphs = listcache.ListCache(self.max_list_bytes)     # key -> Entry with engine_sig, early, scratch
+        self._list_warm = self._graphs.warm                         # (TrainStep._drop_recorded clears both)
         dev, cap = self.dev, self.arena.capacity
-        lib = L.load()
         self._zero_e_cap = torch.zeros((max(cap["e"], 1), 128), dtype=torch.float32, device=dev)
         self._zero_views = {}
-        self._scratch = dict(
-            _zero_e=None, _dw_ws=None, _dw_ws_main=None,
-            _prep_ws=torch.zeros(max(lib.gfv_prep_workspace_bytes(self.arena.max_graphs) // 4, 1), dtype=torch.float32, device=dev),
-            _fvm_cnt=torch.zeros(4, dtype=torch.int32, device=dev))
+        prep_ws, fvm_cnt = prep_scratch(self.arena.max_graphs, dev)
+        self._scratch = dict(_zero_e=None, _dw_ws=None, _dw_ws_main=None, _prep_ws=prep_ws, _fvm_cnt=fvm_cnt)
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------
     def stats(self):
-        return dict(self._counts, lists=len(self._graphs), list_bytes=sum(e.bytes for e in self._graphs.values()))
+        return self._graphs.stats()
 
     def set_batch(self, graphs):
         raise TypeError("PoolTrainStep takes its batch per step: step(indices)")
@@ -139,7 +122,7 @@ class PoolTrainStep(TrainStep):
             if grown[0]:
                 # ... and no list recorded against the old one survives.  The warm-up counts stay: what a key needs of the
                 # workspace depends on its sizes alone, and the new one is at least as large
-                self._graphs.clear()
+                self._graphs.clear(keep_warm=True)
 
     def _valid(self, ent):
         return ent.engine_sig == self.engine.capture_signature() and ent.scratch == self._scratch_ptrs()
@@ -164,29 +147,23 @@ class PoolTrainStep(TrainStep):
         acc = self.model.node_norm.should_accumulate()
         dist_on = self.dist_on
         key = (sig, acc, dist_on)
-        listed = self.use_graph == "list" and self.max_list_bytes > 0 and not (acc and dist_on) and key not in self._oversize
+        listed = self.use_graph == "list" and not (acc and dist_on)
         recorded = None
         with self._own_scratch(plan.E) as grown:
-            ent = self._graphs.get(key) if listed else None
+            ent = self._graphs.get(key)
             if ent is not None and not self._valid(ent):
                 # something a recorded launch points at moved (weight-image set, product form, a piece of scratch): the list is
                 # dropped and this step runs eager - a stale list is never issued
-                del self._graphs[key]
-                self._list_warm[key] = 0            # (this eager step is the first of the key's new warm-up)
-                ent = None
-            if ent is not None:
-                self._graphs.move_to_end(key)
+                self._graphs.invalidate(key)
+            what = self._graphs.decide(key, listed)
+            if what == "replay":
                 ent.cl.replay()
                 self.losses, self.uvp_node, self.uvp_cell = ent.outs
                 if dist_on:
                     self._allreduce(ent.early)
                     self._adam()
-                self._counts["replayed"] += 1
-            elif not listed or self._list_warm.get(key, 0) < PoolTrainStep.WARM:
-                if listed:
-                    self._list_warm[key] = self._list_warm.get(key, 0) + 1
+            elif what == "eager":
                 self._eager(acc, dist_on)
-                self._counts["eager"] += 1
             else:
                 before = torch.cuda.memory_reserved(self.dev)
                 with cmdlist.record() as cl:
@@ -195,22 +172,11 @@ class PoolTrainStep(TrainStep):
                 if dist_on:
                     self._allreduce(early)
                     self._adam()
-                self._counts["recorded"] += 1
                 recorded = (cl, early, nbytes)
         if recorded is not None and not grown[0]:    # (a workspace that moved while the list was recorded: the list is not kept)
             cl, early, nbytes = recorded
-            if nbytes > self.max_list_bytes:
-                self._oversize.add(key)
-            else:
-                self._graphs[key] = _Recorded(cl, self.engine.capture_signature(), early, self._scratch_ptrs(), nbytes,
-                                              (self.losses, self.uvp_node, self.uvp_cell))
-                while sum(e.bytes for e in self._graphs.values()) > self.max_list_bytes and len(self._graphs) > 1:
-                    old, _ = self._graphs.popitem(last=False)
-                    # a key that keeps losing its list to the byte budget would record on every visit (a recording allocates a
-                    # whole step's activations afresh): after EVICT_MAX evictions it stays eager
-                    self._evicted[old] = self._evicted.get(old, 0) + 1
-                    if self._evicted[old] >= PoolTrainStep.EVICT_MAX:
-                        self._oversize.add(old)
+            self._graphs.store(key, listcache.Entry(cl, nbytes, (self.losses, self.uvp_node, self.uvp_cell), early=early,
+                                                    engine_sig=self.engine.capture_signature(), scratch=self._scratch_ptrs()))
         if acc:
             self.model.node_norm.note_accumulated()
         if self._accum is not None:

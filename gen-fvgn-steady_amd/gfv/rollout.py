@@ -14,20 +14,12 @@ step's residual losses and update norms to a device-resident history.
 Launch modes.  "cmd_list" (default): the step is issued eagerly twice (which settles the weight-image set), recorded once with
 `gfv.cmdlist.record` and replayed from then on; "eager": launch by launch.  The two give the same bits.
 
-Who owns what a recorded list points at.  The list's own allocations (activations, outputs) live in the private memory pool of
-the `CommandList`; inside it the forward frees and re-uses blocks, which is correct in stream order because the forward-only
-step issues every launch on ONE stream (its weight images are static: no side-stream build, no fork).  Everything else the list
-reads is created in set-up and held by this object for its lifetime, never reallocated: `x`, `x_backup`, the history, the step
-counter, the reduction workspace, the engine scratch of the input preparation and of the finite-volume tail (swapped into the
-engine for the duration of a step, so that another batch run through the same engine cannot replace them), the padded
-parameters of a narrow model, the plan and the graphs.  The weight images belong to the engine's image set of this parameter
-set, which the engine keeps (also after it has been superseded).
+Who owns what a recorded list points at: DESIGN.md 5l.  Particular to this object, created in set-up and held for its lifetime,
+never reallocated: `x`, `x_backup`, the history, the step counter, the reduction workspace, the plan and the graphs.
 
 Weights.  Images (and, for hidden_size < 128, the padded copies) are built ONCE - in the constructor and in
-`refresh_weights()` - not per step: the parameters of a model that is being run do not change.  Each `step()` compares the
-parameters' storage and in-place version counters and the parts of `Engine.capture_signature()` a forward-only list depends on
-(parameter set, product form, identity of the image set) with what the images were built for and raises on a mismatch instead
-of replaying stale images: after `load_state_dict`, an optimizer step or `.to()`, call `refresh_weights()`.
+`refresh_weights()` - not per step (gfv/static_forward.py).  Each `step()` raises on a parameter or engine change instead of
+replaying stale images: after `load_state_dict`, an optimizer step or `.to()`, call `refresh_weights()`.
 
 Normalizer.  As in the reference loop the model is called with `norm_global` every step, and `accumulate` follows
 `node_norm.should_accumulate()` exactly as `NNmodel.forward` does - for a trained model (accumulation count reached) that is
@@ -46,15 +38,15 @@ a trained model.  `anderson=0` (the default) issues no new launch and allocates 
 """
 from __future__ import annotations
 
-import contextlib
-
 import torch
 
 from . import anderson as AA
 from . import cmdlist
 from . import lib as L
 from .functions import require_gpu
+from .listcache import WARM, ListCache
 from .plan import get_plan
+from .static_forward import StaticForward, WeightGuard  # noqa: F401  (WeightGuard: named from here by its users)
 
 HISTORY_WIDTH = 6   # (loss_cont, loss_mom_x, loss_mom_y, loss_press, ||uvp_new - uvp_prev||_2, ||uvp_new||_2) per graph
 
@@ -67,31 +59,8 @@ def check_room(steps_done, max_steps, steps=1):
                          "(the device history has one row per step); reset() or build the Rollout with a larger max_steps")
 
 
-class WeightGuard:
-    """What the weight images of a Rollout were built for: the storage and in-place version of every parameter and Normalizer
-    buffer location.  `check()` raises when any of them changed since `refresh()`."""
-
-    def __init__(self, model):
-        self.model = model
-        self.sig = None
-        self.refresh()
-
-    def signature(self):
-        _, tensors = self.model.param_names_tensors()
-        return (tuple(t._version for t in tensors), tuple(t.data_ptr() for t in tensors),
-                tuple(b.data_ptr() for b in self.model.node_norm.buffers_dict().values()))
-
-    def refresh(self):
-        self.sig = self.signature()
-
-    def check(self):
-        if self.signature() != self.sig:
-            raise RuntimeError("Rollout: the model's parameters changed (load_state_dict, an optimizer step, .to()) since the "
-                               "weight images were built; call refresh_weights() before the next step")
-
-
 class Rollout:
-    WARM = 2   # eager steps before a list is recorded (they are steps of the rollout like any other)
+    WARM = WARM   # eager steps before a list is recorded (they are steps of the rollout like any other)
 
     def __init__(self, model, graphs, max_steps=1000, launch_mode="cmd_list", norm_global=None, anderson=0, anderson_beta=1.0,
                  anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0):
@@ -124,62 +93,27 @@ class Rollout:
         self.history = torch.zeros((self.max_steps, pl.B, HISTORY_WIDTH), dtype=torch.float32, device=dev)
         self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # (step counter, arrival counter)
         self._partial = torch.zeros((pl.n_chunks, 2), dtype=torch.float64, device=dev)
-        lib = L.load()
-        self._prep_ws = torch.zeros(max(lib.gfv_prep_workspace_bytes(pl.B) // 4, 1), dtype=torch.float32, device=dev)
-        self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)
         L.status_mirror()
         self.anderson = aa_args[0]
         self._aa = AA.AndersonState(pl, dev, self.max_steps, *aa_args) if self.anderson else None
         self.steps_done = 0
-        self._lists, self._warm = {}, {}
+        self._lists = ListCache(None, dev=dev)      # accumulate -> the recorded step; unbounded: two keys at most
         self._outs = None
-        self._guard = WeightGuard(model)
-        self.refresh_weights()
+        self._fwd = StaticForward(model, pl.B, dev)
 
     # ---- weights -------------------------------------------------------------------------------------------------------
     def refresh_weights(self):
         """(Re)build what depends on the parameter VALUES: padded copies (hidden_size < 128) and the forward weight images.
         Recorded lists are dropped (the next steps warm up and record again)."""
-        from FVMmodel.padding import pad_parameters
-        names, tensors = self.model.param_names_tensors()
-        with torch.no_grad():
-            padded = pad_parameters(names, tensors, self.model.hidden_size)
-            self.P = dict(zip(names, (t.detach() for t in padded)))
-        self.buffers = self.model.node_norm.buffers_dict()
-        self.model.node_norm._host_num_acc = None
-        self._lists, self._warm = {}, {}
-        with self.engine.model_width():
-            self.engine.build_static_images(self.P)
-        self._guard.refresh()
-        self._sig = self._engine_signature()
+        self._fwd.refresh()
+        self._lists.clear()
 
-    def _engine_signature(self):
-        """The parts of Engine.capture_signature() a forward-only list depends on: the parameter set the image set belongs to,
-        the product form, and the image set itself (images are added to a set, never moved; the descriptor table of the per-step
-        rebuild is not part of a list that builds no images)."""
-        sig = self.engine.capture_signature()
-        wi = self.engine._wi
-        return (sig[0], sig[2], None if wi is None else id(wi["fwd"]))
+    P = property(lambda self: self._fwd.P)
 
     # ---- one step ------------------------------------------------------------------------------------------------------
-    @contextlib.contextmanager
-    def _own_scratch(self):
-        eng = self.engine
-        saved = (eng._prep_ws, eng._fvm_cnt)
-        eng._prep_ws, eng._fvm_cnt = self._prep_ws, self._fvm_cnt
-        try:
-            yield
-        finally:
-            assert eng._prep_ws is self._prep_ws and eng._fvm_cnt is self._fvm_cnt, "engine scratch was reallocated inside a step"
-            eng._prep_ws, eng._fvm_cnt = saved
-
     def _body(self, acc):
         pl = self.plan
-        with self._own_scratch(), self.engine.model_width():
-            losses, uvp_node, uvp_cell, _, sv = self.engine.forward(
-                self.P, self.buffers, self.x, pl, norm_global=self.norm_global, accumulate=acc, want_outputs=True,
-                want_edge_attr15=False, x_raw=self.x_backup, keep=False, static_weights=True)
-        assert sv is None
+        losses, uvp_node, uvp_cell = self._fwd.forward(self.x, self.x_backup, pl, acc, self.norm_global)
         if self._aa is not None:
             self._aa.launch(uvp_node, self.x_backup, self._state)
         L.check(L.load().gfv_rollout_advance(
@@ -195,26 +129,12 @@ class Rollout:
         advanced to (the mixed one where the step was accelerated)."""
         L.raise_on_status("Rollout.step")
         check_room(self.steps_done, self.max_steps)
-        self._guard.check()
-        if self._engine_signature() != self._sig:
-            raise RuntimeError("Rollout: the engine's weight-image set changed under the rollout (another parameter set or product "
-                               "form went through the same engine); call refresh_weights()")
+        self._fwd.check("Rollout", "rollout")
         norm = self.model.node_norm
         acc = self.norm_global and norm.should_accumulate()
-        if self.launch_mode == "eager" or cmdlist.active() is not None or torch.cuda.is_current_stream_capturing():
-            outs = self._body(acc)
-        else:
-            ent = self._lists.get(acc)
-            if ent is not None:
-                ent[0].replay()
-                outs = ent[1]
-            elif self._warm.get(acc, 0) < Rollout.WARM:
-                self._warm[acc] = self._warm.get(acc, 0) + 1
-                outs = self._body(acc)
-            else:
-                with cmdlist.record() as cl:
-                    outs = self._body(acc)
-                self._lists[acc] = (cl, outs)
+        # (a recording or a stream capture that is already open takes the step eagerly, and counts no warm-up)
+        listed = self.launch_mode == "cmd_list" and cmdlist.active() is None and not torch.cuda.is_current_stream_capturing()
+        outs = self._lists.run(acc, lambda: self._body(acc), listed)
         if acc:
             norm.note_accumulated()
         self.steps_done += 1

@@ -17,14 +17,9 @@ The step is `Rollout._body` over the arena's plan and `x` / `x_raw` - the forwar
 criterion is evaluated there, and a slot whose `done` is set keeps its state whatever is queued behind it.  That is what lets the
 host run ahead without synchronising (`max_ahead`) and makes an entry's result independent of its neighbours.
 
-Recorded lists are kept per ordered batch signature (variants of one mesh share it: one list serves the whole sweep): two eager
-warm-up steps, then record, then replay; bounded by `max_list_bytes`, least recently used out.
-
-Who owns what a recorded list points at.  (1) The list's private memory pool: activations and outputs.  (2) The arena: the plan,
-`x`, `x_raw`.  (3) This object, for its lifetime, never reallocated: `ctl`, `slots`, `last`, `state3`, the reduction workspace,
-the counters, the pinned mirror, the padded parameters of a narrow model and the engine scratch of the input preparation and of
-the finite-volume tail, sized for `max_graphs` and swapped into the engine for the duration of a step (`Rollout._own_scratch`'s
-rule).  (4) The engine's static weight-image set (checked against `WeightGuard` and the engine signature before a run).
+Recorded lists are kept per ordered batch signature (variants of one mesh share it: one list serves the whole sweep) in a
+`gfv.listcache.ListCache` bounded by `max_list_bytes`.  Who owns what a list points at: DESIGN.md 5l.  Particular to this object,
+for its lifetime, never reallocated: `ctl`, `slots`, `last`, `state3`, the reduction workspace, the counters, the pinned mirror.
 
 A swap (the mirror shows a retired slot and something is pending): synchronise; read `slots` / `last` from device memory; pay
 `state3` back into ALL current entries; record the retired entries' results; load the new index list; zero the swapped slots.
@@ -33,17 +28,16 @@ The mirror is only a hint that a synchronisation is worth it - every value acted
 from __future__ import annotations
 
 import collections
-import contextlib
 import ctypes as C
 import math
 import struct
 
 import torch
 
-from . import cmdlist
 from . import lib as L
+from . import listcache
 from .functions import require_gpu
-from .rollout import WeightGuard
+from .static_forward import StaticForward, check_normalizer
 
 SweepResult = collections.namedtuple("SweepResult", "entry steps converged losses rel_update")
 
@@ -110,16 +104,8 @@ class SlotScheduler:
         return tuple(self.sig[e] for e in self.slots)
 
 
-class _Recorded:
-    __slots__ = ("cl", "bytes")
-
-    def __init__(self, cl, nbytes):
-        self.cl, self.bytes = cl, nbytes
-
-
 class Sweep:
-    WARM = 2        # eager steps of a batch signature before its list is recorded (they are steps of the sweep like any other)
-    EVICT_MAX = 2   # a signature that lost its list to the byte budget this often stays eager (PoolTrainStep's rule)
+    WARM, EVICT_MAX = listcache.WARM, listcache.EVICT_MAX
 
     def __init__(self, model, pool, max_graphs=8, tol=1e-6, max_steps=40000, min_steps=1, patience=1, max_ahead=64,
                  launch_mode="cmd_list", max_list_bytes=16 << 30, max_sizes=None):
@@ -134,14 +120,13 @@ class Sweep:
         self.max_ahead = int(max_ahead)
         self.launch_mode, self.max_list_bytes = launch_mode, int(max_list_bytes)
         self.model, self.pool = model, pool
-        self._check_normalizer()
+        check_normalizer(model)
         require_gpu(pool.x[0])
         self.arena = pool.arena(max_graphs, max_sizes)
         self.engine = model.engine()
         dev = self.dev = pool.device
         cap, B = self.arena.capacity, self.arena.max_graphs
         self.norm_global = True        # (what the graphs of a pool carry: gfv.pool.BatchArena._make_views)
-        lib = L.load()
         # device-resident state of the slots and what the advance launch works on: created once, never reallocated
         self._ctl = torch.zeros(4, dtype=torch.int32, device=dev)
         self._slots = torch.zeros((B, 4), dtype=torch.int32, device=dev)
@@ -149,18 +134,14 @@ class Sweep:
         self._state3 = torch.zeros((max(cap["n"], 1), 3), dtype=torch.float32, device=dev)
         self._partial = torch.zeros((max(cap["nchunk"], 1), 2), dtype=torch.float64, device=dev)
         self._state = torch.zeros(2, dtype=torch.int32, device=dev)          # (step sequence number, arrival counter)
-        self._prep_ws = torch.zeros(max(lib.gfv_prep_workspace_bytes(B) // 4, 1), dtype=torch.float32, device=dev)
-        self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)
         self._mirror_words = 1 + 2 * B
         host, devp = C.POINTER(C.c_int32)(), C.c_void_p()
         L.check(L.load(raw=True).gfv_sweep_mirror_create(self._mirror_words, C.byref(host), C.byref(devp)), "gfv_sweep_mirror_create")
         self._mirror, self._mirror_dev = host, devp.value
         L.status_mirror()
-        self._lists = collections.OrderedDict()      # batch signature -> _Recorded, least recently used first
-        self._warm, self._oversize, self._evicted = {}, set(), {}
-        self._counts = dict(steps=0, swaps=0, replayed=0, recorded=0, eager=0)
-        self._guard = WeightGuard(model)
-        self.refresh_weights()
+        self._lists = listcache.ListCache(self.max_list_bytes, dev=dev)      # batch signature -> the recorded step
+        self._counts = dict(steps=0, swaps=0)
+        self._fwd = StaticForward(model, B, dev)
 
     def __del__(self):
         host = getattr(self, "_mirror", None)
@@ -173,57 +154,21 @@ class Sweep:
                 pass
             self._mirror = None
 
-    # ---- guards --------------------------------------------------------------------------------------------------------
-    def _check_normalizer(self):
-        if self.model.node_norm.should_accumulate():
-            raise ValueError("Sweep: the model's Normalizer is still accumulating; its statistics would couple the graphs of a "
-                             "batch, so an entry's result would depend on its neighbours.  Sweep a trained model")
-
+    # ---- weights, one step ---------------------------------------------------------------------------------------------
     def refresh_weights(self):
         """(Re)build what depends on the parameter VALUES: padded copies (hidden_size < 128) and the forward weight images.
         Recorded lists are dropped (the next steps warm up and record again)."""
-        from FVMmodel.padding import pad_parameters
-        names, tensors = self.model.param_names_tensors()
-        with torch.no_grad():
-            padded = pad_parameters(names, tensors, self.model.hidden_size)
-            self.P = dict(zip(names, (t.detach() for t in padded)))
-        self.buffers = self.model.node_norm.buffers_dict()
-        self.model.node_norm._host_num_acc = None
+        self._fwd.refresh()
         self._lists.clear()
-        self._warm = {}
-        with self.engine.model_width():
-            self.engine.build_static_images(self.P)
-        self._guard.refresh()
-        self._sig = self._engine_signature()
 
-    def _engine_signature(self):
-        """As Rollout._engine_signature: parameter set, product form, identity of the image set."""
-        sig = self.engine.capture_signature()
-        wi = self.engine._wi
-        return (sig[0], sig[2], None if wi is None else id(wi["fwd"]))
+    P = property(lambda self: self._fwd.P)
 
     def stats(self):
-        return dict(self._counts, lists=len(self._lists), list_bytes=sum(e.bytes for e in self._lists.values()))
-
-    # ---- one step ------------------------------------------------------------------------------------------------------
-    @contextlib.contextmanager
-    def _own_scratch(self):
-        eng = self.engine
-        saved = (eng._prep_ws, eng._fvm_cnt)
-        eng._prep_ws, eng._fvm_cnt = self._prep_ws, self._fvm_cnt
-        try:
-            yield
-        finally:
-            assert eng._prep_ws is self._prep_ws and eng._fvm_cnt is self._fvm_cnt, "engine scratch was reallocated inside a step"
-            eng._prep_ws, eng._fvm_cnt = saved
+        return dict(self._counts, **self._lists.stats())
 
     def _body(self, graphs, pl):
         x, x_raw = graphs[0].x, graphs[0]._gfv_x_raw
-        with self._own_scratch(), self.engine.model_width():
-            losses, uvp_node, _, _, sv = self.engine.forward(
-                self.P, self.buffers, x, pl, norm_global=self.norm_global, accumulate=False, want_outputs=True,
-                want_edge_attr15=False, x_raw=x_raw, keep=False, static_weights=True)
-        assert sv is None
+        losses, uvp_node, _ = self._fwd.forward(x, x_raw, pl, False, self.norm_global)
         L.check(L.load().gfv_sweep_advance(
             uvp_node.data_ptr(), x_raw.data_ptr(), x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(), pl.chunk_end.data_ptr(),
             pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(), self._ctl.data_ptr(),
@@ -234,32 +179,8 @@ class Sweep:
 
     def _step(self, key, graphs, pl):
         self._counts["steps"] += 1
-        listed = self.launch_mode == "cmd_list" and self.max_list_bytes > 0 and key not in self._oversize
-        ent = self._lists.get(key) if listed else None
-        if ent is not None:
-            self._lists.move_to_end(key)
-            ent.cl.replay()
-            self._counts["replayed"] += 1
-        elif not listed or self._warm.get(key, 0) < Sweep.WARM:
-            if listed:
-                self._warm[key] = self._warm.get(key, 0) + 1
-            self._body(graphs, pl)
-            self._counts["eager"] += 1
-        else:
-            before = torch.cuda.memory_reserved(self.dev)
-            with cmdlist.record() as cl:
-                cl.keep.append(self._body(graphs, pl))
-            nbytes = max(torch.cuda.memory_reserved(self.dev) - before, 0)      # the segments of the list's private pool
-            self._counts["recorded"] += 1
-            if nbytes > self.max_list_bytes:
-                self._oversize.add(key)
-                return
-            self._lists[key] = _Recorded(cl, nbytes)
-            while sum(e.bytes for e in self._lists.values()) > self.max_list_bytes and len(self._lists) > 1:
-                old, _ = self._lists.popitem(last=False)
-                self._evicted[old] = self._evicted.get(old, 0) + 1
-                if self._evicted[old] >= Sweep.EVICT_MAX:
-                    self._oversize.add(old)
+        self._lists.run(key, lambda: self._body(graphs, pl), self.launch_mode == "cmd_list")
+        self._lists.parked = None       # (a list the byte budget refused goes at once: nothing behind the step reads its outputs)
 
     # ---- the run -------------------------------------------------------------------------------------------------------
     def _write_ctl(self):
@@ -282,11 +203,8 @@ class Sweep:
         written back into the pool entries' `x[:, 0:3]`."""
         L.raise_on_status("Sweep.run")
         ents = check_entries(entries, self.pool.n)
-        self._check_normalizer()
-        self._guard.check()
-        if self._engine_signature() != self._sig:
-            raise RuntimeError("Sweep: the engine's weight-image set changed under the sweep (another parameter set or product "
-                               "form went through the same engine); call refresh_weights()")
+        check_normalizer(self.model)
+        self._fwd.check("Sweep", "sweep")
         if not ents:
             return []
         sched = SlotScheduler(ents, lambda e: self.arena.signature([e])[0], self.arena.max_graphs)
