@@ -8,16 +8,15 @@
 //   gfv_anderson_mix    rows of a graph with depth > 0:  uvp_node = g - (1-beta) f - sum_j gamma_j (dG_j - (1-beta) dF_j), j in
 //                       ascending ring slot, in double, rounded to fp32 once.  Rows of a graph with depth 0 are not written.
 // The difference form keeps a row whose g never changes (a Dirichlet node: dG = 0, f = 0 exactly) bit for bit.
-// Summation order as in rollout.hip: one wave per plan chunk (chunks never cross a graph), a lane sums its rows in ascending order
-// in double, the tree of a xor butterfly over the 64 lanes (aa_tree_sum), partials per chunk; the workgroup that arrives last (integer arrival counter, left
-// at zero) folds the chunks of each graph - lane l takes chunks l, l + 64, ... counted from the graph's first chunk - and
-// butterflies again.  No floating-point atomics; the sums of a graph do not depend on its neighbours in the batch.
+// Summation order: csrc/gfv_reduce.h, with the butterfly's tree formed in LDS (aa_tree_sum); the arrival counter is left at zero
+// (all-fence form).  The sums of a graph do not depend on its neighbours in the batch.
 // The column loops are unrolled at compile time over GFV_AA_MAX_DEPTH slots with run-time (wave-uniform) masks: every accumulator
 // has a constant index and stays in a register.
 #include "../../include/gfv.h"
 #include "gfv_common.h"
 #include "gfv_launch.h"
 #include "gfv_prof.h"
+#include "gfv_reduce.h"
 
 namespace {
 
@@ -65,12 +64,6 @@ struct MixArgs {
   int N, n_chunks, B, K_max, m;
 };
 
-__device__ __forceinline__ int aa_graph_of(const int* gchunk_ptr, int B, int c) {
-  int b = 0;
-  while (b < B - 1 && gchunk_ptr[b + 1] <= c) ++b;
-  return b;
-}
-
 // the ring slots that hold a valid column: the mk newest, counted back from `newest`
 __device__ __forceinline__ int aa_valid_mask(int newest, int mk, int m) {
   int mask = 0;
@@ -83,7 +76,7 @@ __device__ __forceinline__ int aa_valid_mask(int newest, int mk, int m) {
   return mask;
 }
 
-// The butterfly of aa_wave_sum for AA_P sums at once.  Every lane has put its AA_P values into the wave's LDS tile t[q][lane]
+// The butterfly of gfv_wave_sum for AA_P sums at once.  Every lane has put its AA_P values into the wave's LDS tile t[q][lane]
 // (rows padded to AA_LD); lane q then adds the 64 values of row q in the butterfly's own tree - level o = 32, 16, ... 1:
 // v[l] = v[l] + v[l + o] for l < o, which is what lane 0 of the butterfly computes (v[l] + v[l ^ o], addition commutes) - so the
 // result has the butterfly's bits, at 64 independent LDS reads per lane instead of 6 dependent exchanges per sum.
@@ -108,14 +101,13 @@ __device__ __forceinline__ double aa_tree_sum(const double* row) {
 __device__ __forceinline__ bool aa_finite(double v) { return fabs(v) <= 1.79769313486231570815e308; }   // false for NaN
 
 __global__ __launch_bounds__(64 * AA_WAVES) void anderson_gram_kernel(const GramArgs A) {
-  __shared__ int s_last;
   __shared__ double s_tile[AA_WAVES][AA_P][AA_LD];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = blockIdx.x * AA_WAVES + wave;
   const int m = A.m;
   double (*tile)[AA_LD] = s_tile[wave];
   if (c < A.n_chunks) {
-    const int b = aa_graph_of(A.gchunk_ptr, A.B, c);
+    const int b = gfv_chunk_graph(A.gchunk_ptr, A.B, c);
     const int* st = A.aa_state + 4 * b;
     const int cnt = __builtin_amdgcn_readfirstlane(min(max(st[0], 0), m));
     const int head = __builtin_amdgcn_readfirstlane(min(max(st[1], 0), m - 1));
@@ -178,13 +170,8 @@ __global__ __launch_bounds__(64 * AA_WAVES) void anderson_gram_kernel(const Gram
     aa_wave_sync();
     if (lane < AA_P) A.partial[(size_t)AA_P * c + lane] = aa_tree_sum(tile[lane]);      // lane q folds sum q
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(A.counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  const int k = __hip_atomic_load(A.step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!gfv_arrive_last_all_fence(A.counter)) return;
+  const int k = gfv_ld_agent(A.step);
   const bool room = k >= 0 && k < A.K_max;    // (a full table is not written past and nothing is mixed: the host raises before)
   for (int b = wave; b < A.B; b += AA_WAVES) {
     const int c0 = A.gchunk_ptr[b], c1 = min(A.gchunk_ptr[b + 1], A.n_chunks);
@@ -196,13 +183,7 @@ __global__ __launch_bounds__(64 * AA_WAVES) void anderson_gram_kernel(const Gram
     const int mk = min(cnt + has_prev, m);
     const int vmask = __builtin_amdgcn_readfirstlane(has_prev ? aa_valid_mask(head, mk, m) : 0);
     double s[AA_P];
-#pragma unroll
-    for (int q = 0; q < AA_P; ++q) s[q] = 0.0;
-    for (int q = c0 + lane; q < c1; q += 64) {
-      const double* p = A.partial + (size_t)AA_P * q;
-#pragma unroll
-      for (int t = 0; t < AA_P; ++t) s[t] += __hip_atomic_load(p + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    gfv_fold_chunks(A.partial, c0, c1, lane, s);
     aa_wave_sync();                      // (the tile's last readers: this wave's own chunk, or the graph before)
 #pragma unroll
     for (int t = 0; t < AA_P; ++t) tile[t][lane] = s[t];
@@ -317,7 +298,7 @@ __global__ __launch_bounds__(64 * AA_WAVES) void anderson_mix_kernel(const MixAr
   if (c >= A.n_chunks) return;
   const int k = A.step[0];
   if (k < 0 || k >= A.K_max) return;
-  const int b = aa_graph_of(A.gchunk_ptr, A.B, c);
+  const int b = gfv_chunk_graph(A.gchunk_ptr, A.B, c);
   const int depth = (int)A.table[((size_t)k * A.B + b) * 4 + 2];
   if (depth <= 0) return;
   double gam[MD];

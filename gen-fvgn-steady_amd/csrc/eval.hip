@@ -8,14 +8,12 @@
 // The entry of every graph and its "has a target" bit travel by value in the launch's argument block (as the indices of
 // gfv_pool_assemble do: a buffer the host rewrites for the next batch would race with a launch that is still queued), so the
 // launch is issued eagerly behind a replayed step and is never part of a recorded list.
-// Summation order as in sweep.hip / rollout.hip: one wave per plan chunk (chunks never cross a graph), differences in fp32, squares
-// and sums in double, a lane sums its rows in ascending order, a xor butterfly over the 64 lanes; the workgroup that arrives last
-// (integer arrival counter, left at zero) folds the chunks of each graph - lane l takes chunks l, l + 64, ... - butterflies again,
-// takes the square roots in double and rounds to fp32.  No floating-point atomics: the same bits run after run.
+// Summation order: csrc/gfv_reduce.h (twelve sums per chunk; the arrival counter is left at zero; all-fence form).
 #include "../../include/gfv.h"
 #include "gfv_common.h"
 #include "gfv_launch.h"
 #include "gfv_prof.h"
+#include "gfv_reduce.h"
 
 namespace {
 
@@ -41,19 +39,11 @@ struct EvalArgs {
   int entry[MAXB];
 };
 
-__device__ __forceinline__ double ev_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * EV_WAVES) void eval_collect_kernel(const EvalArgs A) {
-  __shared__ int s_last;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = blockIdx.x * EV_WAVES + wave;
   if (c < A.n_chunks) {
-    int b = 0;   // the chunk's graph
-    while (b < A.B - 1 && A.gchunk_ptr[b + 1] <= c) ++b;
+    const int b = gfv_chunk_graph(A.gchunk_ptr, A.B, c);
     const bool tgt = (A.has_target >> b) & 1ull;
     const int beg = A.chunk_beg[c], end = min(A.chunk_end[c], A.N);
     double s[EV_SUMS];
@@ -76,34 +66,23 @@ __global__ __launch_bounds__(64 * EV_WAVES) void eval_collect_kernel(const EvalA
       }
     }
 #pragma unroll
-    for (int k = 0; k < EV_SUMS; ++k) s[k] = ev_wave_sum(s[k]);
+    for (int k = 0; k < EV_SUMS; ++k) s[k] = gfv_wave_sum(s[k]);
     if (lane == 0) {
       double* p = A.partial + (size_t)EV_SUMS * c;
 #pragma unroll
       for (int k = 0; k < EV_SUMS; ++k) p[k] = s[k];
     }
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(A.counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
+  if (!gfv_arrive_last_all_fence(A.counter)) return;
   for (int b = wave; b < A.B; b += EV_WAVES) {
     const int c0 = A.gchunk_ptr[b], c1 = min(A.gchunk_ptr[b + 1], A.n_chunks);
     const bool tgt = (A.has_target >> b) & 1ull;
     double s[EV_SUMS];
-#pragma unroll
-    for (int k = 0; k < EV_SUMS; ++k) s[k] = 0.0;
-    for (int q = c0 + lane; q < c1; q += 64) {
-      const double* p = A.partial + (size_t)EV_SUMS * q;
-#pragma unroll
-      for (int k = 0; k < EV_SUMS; ++k) s[k] += __hip_atomic_load(p + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    gfv_fold_chunks(A.partial, c0, c1, lane, s);
     double mine = 0.0;          // lane 4 + k keeps sum k
 #pragma unroll
     for (int k = 0; k < EV_SUMS; ++k) {
-      const double v = ev_wave_sum(s[k]);
+      const double v = gfv_wave_sum(s[k]);
       if (lane == 4 + k) mine = v;
     }
     // (per-lane vector stores: one lane per column of the record)

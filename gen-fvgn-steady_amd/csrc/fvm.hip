@@ -8,6 +8,7 @@
 // normalised 5x5 matrices) are built once per mesh batch.
 #include "gfv_common.h"
 #include "gfv_prof.h"
+#include "gfv_reduce.h"
 #include "../../include/gfv.h"
 
 namespace {
@@ -687,7 +688,6 @@ __global__ __launch_bounds__(1024) void fvm_tail_kernel(const float* __restrict_
                                                        const float* __restrict__ uvp_dim, const float* __restrict__ phi, int smooth,
                                                        float* __restrict__ out, int N) {
   __shared__ float red[4][1024];
-  __shared__ int last;
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= B) {
     const int i = ((int)blockIdx.x - B) * 1024 + tid;
@@ -750,24 +750,16 @@ __global__ __launch_bounds__(1024) void fvm_tail_kernel(const float* __restrict_
     losses[4 * b + 1] = sqrtf(S1) * sigma[(size_t)b * 3];
     losses[4 * b + 2] = sqrtf(S2) * sigma[(size_t)b * 3 + 1];
     losses[4 * b + 3] = sqrtf(S3);
-    last = 0;
-    if (hyper) {
-      __threadfence();
-      last = atomicAdd(counter, 1) == B - 1;
-    }
   }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
+  // (the losses are thread 0's own stores; forward only - no hyper - nothing is counted and nobody is last)
+  if (!gfv_arrive_last_leader_fence(counter, B, hyper != nullptr)) return;
   // train_loss_kernel (csrc/misc.hip) by the first 64 threads of the workgroup that saw every graph's losses written
   const float wc = hyper[5], wm = hyper[6], wp = hyper[7];
   float s = 0.f;
   if (tid < 64) {
     for (int g = tid; g < B; g += 64) {
-      const float l0 = __hip_atomic_load(losses + 4 * g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float l1 = __hip_atomic_load(losses + 4 * g + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float l2 = __hip_atomic_load(losses + 4 * g + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const float l3 = __hip_atomic_load(losses + 4 * g + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float l0 = gfv_ld_agent(losses + 4 * g), l1 = gfv_ld_agent(losses + 4 * g + 1);
+      const float l2 = gfv_ld_agent(losses + 4 * g + 2), l3 = gfv_ld_agent(losses + 4 * g + 3);
       const float tot = wp * l3 + wc * l0 + wm * l1 + wm * l2;
       s += logf(tot);
       const float inv = 1.0f / (tot * (float)B);

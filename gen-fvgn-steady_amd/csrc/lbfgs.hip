@@ -14,7 +14,7 @@
 //                       count live on the device), runs the recursion in double, writes delta, g.d and the result block
 //   gfv_lbfgs_combine   d = -sum_j delta_j b_j, the per-element sum in double rounded once;  max|d|
 //   gfv_lbfgs_dot       masked copy of a gradient + its dot with d, max|.|, ||.||_1 (a line-search trial point): the workgroup
-//                       that arrives last (an integer arrival counter, left at zero: csrc/rollout.hip) folds the partials
+//                       that arrives last (an integer arrival counter, left at zero: csrc/gfv_reduce.h, all-fence form) folds
 //   gfv_lbfgs_axpy      p = x0 + t d on the non-padding elements
 //
 // INVARIANT - padding is not data.  The flat layout starts every tensor on a 16-byte boundary (gfv.engine.GradStore) and the
@@ -28,6 +28,7 @@
 #include "../../include/gfv.h"
 #include "gfv_common.h"
 #include "gfv_launch.h"
+#include "gfv_reduce.h"
 
 namespace {
 
@@ -39,16 +40,6 @@ constexpr int LB_TILE4 = LB_THREADS * LB_Q;
 constexpr int LB_COEF_THREADS = 1024;
 constexpr int LB_PARTS = 4;
 
-__device__ __forceinline__ double lb_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float lb_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 __device__ __forceinline__ double lb_dot4(const float4 a, const float4 b, double acc) {
   acc += (double)a.x * (double)b.x;
   acc += (double)a.y * (double)b.y;
@@ -140,9 +131,9 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_multidot_kernel(const float4
         a1 = lb_dot4(v[u][q], ry[q], a1);
         a2 = lb_dot4(v[u][q], rg[q], a2);
       }
-      a0 = lb_wave_sum(a0);
-      a1 = lb_wave_sum(a1);
-      a2 = lb_wave_sum(a2);
+      a0 = gfv_wave_sum(a0);
+      a1 = gfv_wave_sum(a1);
+      a2 = gfv_wave_sum(a2);
       if (lane == 0 && j0 + u < rows) {   // (past the end: the last row again, not stored)
         s_acc[phys[u]][wave][0] = a0;
         s_acc[phys[u]][wave][1] = a1;
@@ -161,11 +152,11 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_multidot_kernel(const float4
       l1 += ((double)fabsf(rg[q].x) + (double)fabsf(rg[q].y)) + ((double)fabsf(rg[q].z) + (double)fabsf(rg[q].w));
       mx = fmaxf(fmaxf(mx, fmaxf(fabsf(rg[q].x), fabsf(rg[q].y))), fmaxf(fabsf(rg[q].z), fabsf(rg[q].w)));
     }
-    a0 = lb_wave_sum(a0);
-    a1 = lb_wave_sum(a1);
-    a2 = lb_wave_sum(a2);
-    l1 = lb_wave_sum(l1);
-    mx = lb_wave_max(mx);
+    a0 = gfv_wave_sum(a0);
+    a1 = gfv_wave_sum(a1);
+    a2 = gfv_wave_sum(a2);
+    l1 = gfv_wave_sum(l1);
+    mx = gfv_wave_max_shfl(mx);
     if (lane == 0) {
       s_acc[2 * m1][wave][0] = a0;
       s_acc[2 * m1][wave][1] = a1;
@@ -240,7 +231,7 @@ __global__ __launch_bounds__(LB_COEF_THREADS) void lbfgs_coef_kernel(const CoefA
   if (tid >= 64) return;
   // ---- one wave from here on -------------------------------------------------------------------------------------
   const double* M = A.M;
-  auto ldM = [&](int row, int r) { return __hip_atomic_load(M + (size_t)row * R + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
+  auto ldM = [&](int row, int r) { return gfv_ld_agent(M + (size_t)row * R + r); };
   double H = A.res[4];
   int accepted = 0;
   if (A.mode == 1) {
@@ -277,7 +268,7 @@ __global__ __launch_bounds__(LB_COEF_THREADS) void lbfgs_coef_kernel(const CoefA
     for (int e = 0; e < E; ++e) {
       if (lane + 64 * e < R && cf[e] != 0.0) acc += cf[e] * ldM(row, phys[e]);
     }
-    return lb_wave_sum(acc);
+    return gfv_wave_sum(acc);
   };
   auto add_at = [&](int r, double v) {
 #pragma unroll
@@ -348,7 +339,7 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_combine_kernel(const float4*
     d[i] = o;
     mx = fmaxf(fmaxf(fabsf(o.x), fabsf(o.y)), fmaxf(fabsf(o.z), fabsf(o.w)));
   }
-  mx = lb_wave_max(mx);
+  mx = gfv_wave_max_shfl(mx);
   // non-negative floats order as their bits: an integer maximum, exact and independent of the order of arrival
   if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(reinterpret_cast<unsigned int*>(res + 8), __float_as_uint(mx));
 }
@@ -356,7 +347,6 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_combine_kernel(const float4*
 __global__ __launch_bounds__(LB_THREADS) void lbfgs_dot_kernel(const float4* a, const unsigned int* mask, float4* copy_out,
                                                                const float4* b, long n4, double* partial, int* counter, double* out) {
   __shared__ double s_red[4][3];
-  __shared__ int s_last;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   double dot = 0.0, l1 = 0.0;
   float mx = 0.f;
@@ -378,9 +368,9 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_dot_kernel(const float4* a, 
       mx = fmaxf(fmaxf(mx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
     }
   }
-  dot = lb_wave_sum(dot);
-  l1 = lb_wave_sum(l1);
-  mx = lb_wave_max(mx);
+  dot = gfv_wave_sum(dot);
+  l1 = gfv_wave_sum(l1);
+  mx = gfv_wave_max_shfl(mx);
   if (lane == 0) { s_red[wave][0] = dot; s_red[wave][1] = (double)mx; s_red[wave][2] = l1; }
   __syncthreads();
   if (tid == 0) {
@@ -389,22 +379,17 @@ __global__ __launch_bounds__(LB_THREADS) void lbfgs_dot_kernel(const float4* a, 
     p[1] = fmax(fmax(s_red[0][1], s_red[1][1]), fmax(s_red[2][1], s_red[3][1]));
     p[2] = ((s_red[0][2] + s_red[1][2]) + s_red[2][2]) + s_red[3][2];
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(counter, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
+  if (!gfv_arrive_last_all_fence(counter)) return;
   dot = 0.0; l1 = 0.0;
   double dmx = 0.0;
   for (int w = tid; w < (int)gridDim.x; w += LB_THREADS) {
-    dot += __hip_atomic_load(partial + 3 * (size_t)w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    dmx = fmax(dmx, __hip_atomic_load(partial + 3 * (size_t)w + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    l1 += __hip_atomic_load(partial + 3 * (size_t)w + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    dot += gfv_ld_agent(partial + 3 * (size_t)w);
+    dmx = fmax(dmx, gfv_ld_agent(partial + 3 * (size_t)w + 1));
+    l1 += gfv_ld_agent(partial + 3 * (size_t)w + 2);
   }
-  dot = lb_wave_sum(dot);
-  l1 = lb_wave_sum(l1);
-  mx = lb_wave_max((float)dmx);
+  dot = gfv_wave_sum(dot);
+  l1 = gfv_wave_sum(l1);
+  mx = gfv_wave_max_shfl((float)dmx);
   __syncthreads();
   if (lane == 0) { s_red[wave][0] = dot; s_red[wave][1] = (double)mx; s_red[wave][2] = l1; }
   __syncthreads();

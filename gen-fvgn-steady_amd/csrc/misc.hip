@@ -3,6 +3,7 @@
 // (pre_train_Adam.py:79,191).  All HBM-bound elementwise / small-reduction work.
 #include "gfv_common.h"
 #include "gfv_prof.h"
+#include "gfv_reduce.h"
 #include "../../include/gfv.h"
 
 namespace {
@@ -231,7 +232,6 @@ __global__ __launch_bounds__(256) void prep_stats_kernel(const float* __restrict
                                                          const float* acc_count, const float* acc_sum, const float* acc_sq,
                                                          float* __restrict__ mean_std) {
   __shared__ double red[4][6];
-  __shared__ int last;
   const int b = blockIdx.y, blk = blockIdx.x, tid = threadIdx.x;
   const int beg = gnode_ptr[b], end = gnode_ptr[b + 1];
   double s[3] = {0.0, 0.0, 0.0}, q[3] = {0.0, 0.0, 0.0};
@@ -250,32 +250,20 @@ __global__ __launch_bounds__(256) void prep_stats_kernel(const float* __restrict
     }
   }
 #pragma unroll
-  for (int c = 0; c < 3; ++c) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) {
-      s[c] += __shfl_xor(s[c], o);
-      q[c] += __shfl_xor(q[c], o);
-    }
-  }
+  for (int c = 0; c < 3; ++c) { s[c] = gfv_wave_sum(s[c]); q[c] = gfv_wave_sum(q[c]); }
   if ((tid & 63) == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) { red[tid >> 6][c] = s[c]; red[tid >> 6][3 + c] = q[c]; }
   }
   __syncthreads();
   if (tid < 6) ws[((size_t)b * NORM_NB + blk) * 6 + tid] = (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-  __syncthreads();
-  if (tid == 0) {
-    __threadfence();
-    last = atomicAdd(counters + b, 1) == NORM_NB - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  __threadfence();
+  __syncthreads();   // (the six stores are ordered before the leader's fence)
+  if (!gfv_arrive_last_leader_fence(counters + b, NORM_NB)) return;
   // the NORM_NB x 6 partial sums: ONE round trip (a thread each) into LDS, then folded k = 0 .. NORM_NB - 1 in order as
   // graph_norm_final_kernel does (its 2 x 64 dependent loads per thread were most of that launch's 6 us)
   __shared__ double fold[NORM_NB * 6];
   for (int i = tid; i < NORM_NB * 6; i += 256)
-    fold[i] = __hip_atomic_load(ws + (size_t)b * NORM_NB * 6 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    fold[i] = gfv_ld_agent(ws + (size_t)b * NORM_NB * 6 + i);
   __syncthreads();
   if (tid < 3) {
     const double cnt = fmax((double)(end - beg), 1.0);
@@ -514,28 +502,23 @@ __device__ __forceinline__ void adam_step(float* __restrict__ p, const float* __
       }
     }
   }
-  __syncthreads();   // every thread of this workgroup has read the state (the values were consumed by the loop above)
-  if (threadIdx.x == 0) {
-    int* counter = reinterpret_cast<int*>(state) + AS_COUNTER;
-    // RELAXED, no fence: the last arriver needs no DATA of the others, only the fact that they are past their reads of `state`.
-    // (A release fence here writes back the L2's dirty lines - the 14 MB this launch has just written - once per workgroup: the
-    // first form of this kernel took 115 us instead of 8.)
-    if (__hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
-      *counter = 0;
-      if (!skip) {   // (a skipped step is no step: t and the running powers stay)
-        state[AS_T] = t_done + 1.0f;
-        adam_corrections(state, as_get(state, AS_P1) * as_get(state, AS_B1), as_get(state, AS_P2) * as_get(state, AS_B2));
-        if constexpr (EMA) {   // (every workgroup is past its read of ema[EM_W], as of the state)
-          int* rec = reinterpret_cast<int*>(ema);
-          const int k = rec[EM_UPDATES] + 1;
-          rec[EM_UPDATES] = k;
-          ema[EM_W] = ema_weight(ema[EM_DECAY], rec[EM_WARMUP], k);
-        }
+  // every thread of this workgroup has read the state (the loop above consumed the values): the no-data arrival, DESIGN.md 5m
+  int* counter = reinterpret_cast<int*>(state) + AS_COUNTER;
+  if (gfv_arrive_last_nodata(counter)) {
+    *counter = 0;
+    if (!skip) {   // (a skipped step is no step: t and the running powers stay)
+      state[AS_T] = t_done + 1.0f;
+      adam_corrections(state, as_get(state, AS_P1) * as_get(state, AS_B1), as_get(state, AS_P2) * as_get(state, AS_B2));
+      if constexpr (EMA) {   // (every workgroup is past its read of ema[EM_W], as of the state)
+        int* rec = reinterpret_cast<int*>(ema);
+        const int k = rec[EM_UPDATES] + 1;
+        rec[EM_UPDATES] = k;
+        ema[EM_W] = ema_weight(ema[EM_DECAY], rec[EM_WARMUP], k);
       }
-      if (status_host) {
-        const int f = *reinterpret_cast<const volatile int*>(status_dev);
-        if (f) __hip_atomic_store(status_host, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      }
+    }
+    if (status_host) {
+      const int f = *reinterpret_cast<const volatile int*>(status_dev);
+      if (f) __hip_atomic_store(status_host, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
 }
@@ -573,9 +556,7 @@ __global__ __launch_bounds__(ADAM_TPB) void adam_groups_kernel(float* __restrict
 // spread over the grid instead of piling up on workgroup 0).  Nothing outside a segment is read.  Sums are double and every
 // order is fixed: a thread adds its elements in tile order, the lanes of a wave fold by xor butterflies, the four waves in
 // order, and the workgroup that arrives last adds the per-workgroup partials in index order - same inputs, same bits.
-// The hand-off of the partials carries no fence, for the reason written above adam_kernel (the backward has just dirtied the
-// L2 with the gradient): thread 0 stores its workgroup's partial write-through (an agent-scope atomic store), waits for that
-// store, then adds to the arrival counter; the last arriver reads the partials with agent-scope loads that bypass its L1.
+// The hand-off of the partials is the write-through arrival of csrc/gfv_reduce.h: no fence (DESIGN.md 5m says why).
 // ACCUM (gfv_grad_guard_accum_dev): on a hold micro-step every workgroup leaves at once - no norm, no decision, no count.
 constexpr int GUARD_TPB = 256, GUARD_PER_THREAD = 4, GUARD_TILE = GUARD_TPB * GUARD_PER_THREAD, GUARD_MAX_WGS = 256;
 template <bool ACCUM>
@@ -584,7 +565,6 @@ __global__ __launch_bounds__(GUARD_TPB) void grad_guard_kernel(const float* __re
                                                                int* counter, const int* status_dev, const float* __restrict__ accum) {
   __shared__ double red[GUARD_TPB / 64];
   __shared__ double fold[GUARD_MAX_WGS];
-  __shared__ int last;
   if constexpr (ACCUM) {
     if (reinterpret_cast<const int*>(accum)[AC_APPLY] == 0) return;
   }
@@ -611,20 +591,12 @@ __global__ __launch_bounds__(GUARD_TPB) void grad_guard_kernel(const float* __re
       }
     }
   }
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
+  acc = gfv_wave_sum(acc);
   if ((tid & 63) == 0) red[tid >> 6] = acc;
   __syncthreads();
-  if (tid == 0) {
-    const double part = (red[0] + red[1]) + (red[2] + red[3]);
-    __hip_atomic_store(partials + blk, part, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the partial has left this CU before the counter says so
-    last = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblk - 1;
-  }
-  __syncthreads();
-  if (!last) return;
-  for (int i = tid; i < nblk; i += GUARD_TPB)
-    fold[i] = __hip_atomic_load(partials + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid == 0) gfv_st_agent(partials + blk, (red[0] + red[1]) + (red[2] + red[3]));
+  if (!gfv_arrive_last_writethrough(counter)) return;
+  for (int i = tid; i < nblk; i += GUARD_TPB) fold[i] = gfv_ld_agent(partials + i);
   __syncthreads();
   if (tid != 0) return;
   *counter = 0;   // (reusable by the next launch)
@@ -655,8 +627,8 @@ __global__ __launch_bounds__(GUARD_TPB) void grad_guard_kernel(const float* __re
 // Gradient accumulation (include/gfv.h gfv_grad_accum_dev): one launch over the flat gradient between the
 // backward and the norm / Adam launches.  The phase comes from the device record - first (micro == 0): acc = B g, acc not read;
 // middle: acc += B g; last (micro == steps - 1): g = (acc + B g) / (graphs + B), acc not written - so one recorded list serves
-// every micro-step.  Every workgroup reads the record before its loop; the one that arrives last (the arrival pattern of
-// adam_kernel: relaxed, no fence - it needs no data of the others, only that they are past their reads) advances it.
+// every micro-step.  Every workgroup reads the record before its loop; the one that arrives last (the no-data arrival of
+// csrc/gfv_reduce.h, as adam_kernel's: it needs no data of the others, only that they are past their reads) advances it.
 constexpr int ACC_TPB = 256, ACC_MAX_WGS = 512;
 __global__ __launch_bounds__(ACC_TPB) void grad_accum_kernel(float* __restrict__ g, float* __restrict__ acc, long n, int B,
                                                              const float* __restrict__ loss, float* accum) {
@@ -694,25 +666,23 @@ __global__ __launch_bounds__(ACC_TPB) void grad_accum_kernel(float* __restrict__
     }
     for (long i = 4 * n4 + t0; i < n; i += stride) acc[i] = acc[i] + fb * g[i];
   }
-  __syncthreads();   // every thread of this workgroup is past its reads of the record (they chose the branch above)
-  if (threadIdx.x == 0) {
-    if (__hip_atomic_fetch_add(rec + AC_COUNTER, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1) {
-      rec[AC_COUNTER] = 0;
-      const float part = fb * *loss;
-      const float sum = first ? part : accum[AC_LOSS_SUM] + part;
-      if (last) {
-        accum[AC_LOSS_MEAN] = sum / denom;
-        rec[AC_CLOSED] += 1;
-        rec[AC_MICRO] = 0;
-        rec[AC_GRAPHS] = 0;
-        accum[AC_LOSS_SUM] = 0.f;
-        rec[AC_APPLY] = 1;
-      } else {
-        rec[AC_MICRO] = (first ? 0 : micro) + 1;
-        rec[AC_GRAPHS] = (first ? 0 : graphs) + B;
-        accum[AC_LOSS_SUM] = sum;
-        rec[AC_APPLY] = 0;
-      }
+  // every thread of this workgroup is past its reads of the record (they chose the branch above)
+  if (gfv_arrive_last_nodata(rec + AC_COUNTER)) {
+    rec[AC_COUNTER] = 0;
+    const float part = fb * *loss;
+    const float sum = first ? part : accum[AC_LOSS_SUM] + part;
+    if (last) {
+      accum[AC_LOSS_MEAN] = sum / denom;
+      rec[AC_CLOSED] += 1;
+      rec[AC_MICRO] = 0;
+      rec[AC_GRAPHS] = 0;
+      accum[AC_LOSS_SUM] = 0.f;
+      rec[AC_APPLY] = 1;
+    } else {
+      rec[AC_MICRO] = (first ? 0 : micro) + 1;
+      rec[AC_GRAPHS] = (first ? 0 : graphs) + B;
+      accum[AC_LOSS_SUM] = sum;
+      rec[AC_APPLY] = 0;
     }
   }
 }

@@ -5,14 +5,12 @@
 //   history[k, b, 4]   = || uvp_new - uvp_prev ||_2       over the nodes of graph b (uvp_prev: what x_backup[:, 0:3] held)
 //   history[k, b, 5]   = || uvp_new ||_2
 //   k = state[0], advanced by the launch itself (state[0] = k + 1), so that one recorded launch list replays K times.
-// Summation order (fixed, independent of the grid and of timing): the node chunks of the plan (at most a few dozen rows each,
-// never across a graph) - one wave per chunk, a lane sums its rows in ascending order in double, the 64 lanes fold by a xor
-// butterfly; the workgroup that arrives last (an integer arrival counter, state[1], left at zero) folds the chunks of each graph:
-// lane l takes chunks l, l + 64, ... in ascending order, then the same butterfly.  No floating-point atomics.
+// Summation order: csrc/gfv_reduce.h (the arrival counter is state[1], left at zero; all-fence form).
 #include "../../include/gfv.h"
 #include "gfv_common.h"
 #include "gfv_launch.h"
 #include "gfv_prof.h"
+#include "gfv_reduce.h"
 
 namespace {
 
@@ -32,14 +30,7 @@ struct RolloutArgs {
   int N, n_chunks, B, K_max;
 };
 
-__device__ __forceinline__ double ro_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * RO_WAVES) void rollout_advance_kernel(const RolloutArgs A) {
-  __shared__ int s_last;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = blockIdx.x * RO_WAVES + wave;
   if (c < A.n_chunks) {
@@ -47,43 +38,23 @@ __global__ __launch_bounds__(64 * RO_WAVES) void rollout_advance_kernel(const Ro
     double d2 = 0.0, n2 = 0.0;
     for (int i = beg + lane; i < end; i += 64) {
       if (i < 0) continue;
-      const float* u = A.uvp_node + (size_t)i * 3;
-      const float u0 = u[0], u1 = u[1], u2 = u[2];
-      float4* xb = reinterpret_cast<float4*>(A.x_backup + (size_t)i * 12);
-      float4* xo = reinterpret_cast<float4*>(A.x + (size_t)i * 12);
-      float4 r0 = xb[0];
-      const float4 r1 = xb[1], r2 = xb[2];
-      const float e0 = u0 - r0.x, e1 = u1 - r0.y, e2 = u2 - r0.z;
-      d2 += ((double)e0 * (double)e0 + (double)e1 * (double)e1) + (double)e2 * (double)e2;
-      n2 += ((double)u0 * (double)u0 + (double)u1 * (double)u1) + (double)u2 * (double)u2;
-      r0.x = u0; r0.y = u1; r0.z = u2;
-      xb[0] = r0;
-      xo[0] = r0; xo[1] = r1; xo[2] = r2;
+      gfv_advance_row(A.uvp_node, A.x_backup, A.x, i, true, d2, n2);
     }
-    d2 = ro_wave_sum(d2);
-    n2 = ro_wave_sum(n2);
+    d2 = gfv_wave_sum(d2);
+    n2 = gfv_wave_sum(n2);
     if (lane == 0) {
       A.partial[2 * (size_t)c] = d2;
       A.partial[2 * (size_t)c + 1] = n2;
     }
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(A.state + 1, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  const int k = __hip_atomic_load(A.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (!gfv_arrive_last_all_fence(A.state + 1)) return;
+  const int k = gfv_ld_agent(A.state);
   const bool room = k >= 0 && k < A.K_max;   // (a full history is not written past: the host raises before it comes to that)
   for (int b = wave; b < A.B && room; b += RO_WAVES) {
     const int c0 = A.gchunk_ptr[b], c1 = min(A.gchunk_ptr[b + 1], A.n_chunks);
-    double d2 = 0.0, n2 = 0.0;
-    for (int q = c0 + lane; q < c1; q += 64) {
-      d2 += __hip_atomic_load(A.partial + 2 * (size_t)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      n2 += __hip_atomic_load(A.partial + 2 * (size_t)q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    d2 = ro_wave_sum(d2);
-    n2 = ro_wave_sum(n2);
+    double s[2];
+    gfv_fold_chunks(A.partial, c0, c1, lane, s);
+    const double d2 = gfv_wave_sum(s[0]), n2 = gfv_wave_sum(s[1]);
     float* h = A.history + ((size_t)k * A.B + b) * 6;
     if (lane < 4) h[lane] = A.losses[4 * b + lane];
     if (lane == 4) h[4] = (float)sqrt(d2);

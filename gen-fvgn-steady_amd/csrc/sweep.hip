@@ -9,13 +9,12 @@
 //   frozen slot (done != 0):  x = x_backup (x_backup is NOT overwritten);  state3 = x_backup[:, 0:3];  nothing else changes.
 // `done` is read by phase 1 as the launch finds it and written by the workgroup that arrives last, after every workgroup has
 // finished phase 1: the field a slot ends with is the prediction of the step that latched it, whatever is queued behind it.
-// Summation order as in rollout.hip: one wave per plan chunk (chunks never cross a graph), a lane sums its rows in ascending
-// order in double, a xor butterfly over the 64 lanes; the last-arriving workgroup (integer arrival counter, state[1], left at
-// zero) folds the chunks of each graph - lane l takes chunks l, l + 64, ... - and butterflies again.  No floating-point atomics.
+// Summation order: csrc/gfv_reduce.h (the arrival counter is state[1], left at zero; all-fence form).
 #include "../../include/gfv.h"
 #include "gfv_common.h"
 #include "gfv_launch.h"
 #include "gfv_prof.h"
+#include "gfv_reduce.h"
 
 namespace {
 
@@ -44,54 +43,28 @@ struct SweepArgs {
   int N, n_chunks, B;
 };
 
-__device__ __forceinline__ double sw_wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(64 * SW_WAVES) void sweep_advance_kernel(const SweepArgs A) {
-  __shared__ int s_last;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = blockIdx.x * SW_WAVES + wave;
   if (c < A.n_chunks) {
-    int b = 0;   // the chunk's graph
-    while (b < A.B - 1 && A.gchunk_ptr[b + 1] <= c) ++b;
+    const int b = gfv_chunk_graph(A.gchunk_ptr, A.B, c);
     const bool live = A.slots[4 * b + 2] == 0;
     const int beg = A.chunk_beg[c], end = min(A.chunk_end[c], A.N);
     double d2 = 0.0, n2 = 0.0;
     for (int i = beg + lane; i < end; i += 64) {
       if (i < 0) continue;
-      float4* xb = reinterpret_cast<float4*>(A.x_backup + (size_t)i * 12);
-      float4* xo = reinterpret_cast<float4*>(A.x + (size_t)i * 12);
+      const float4 r0 = gfv_advance_row(A.uvp_node, A.x_backup, A.x, i, live, d2, n2);
       float* s3 = A.state3 + (size_t)i * 3;
-      float4 r0 = xb[0];
-      const float4 r1 = xb[1], r2 = xb[2];
-      if (live) {
-        const float* u = A.uvp_node + (size_t)i * 3;
-        const float u0 = u[0], u1 = u[1], u2 = u[2];
-        const float e0 = u0 - r0.x, e1 = u1 - r0.y, e2 = u2 - r0.z;
-        d2 += ((double)e0 * (double)e0 + (double)e1 * (double)e1) + (double)e2 * (double)e2;
-        n2 += ((double)u0 * (double)u0 + (double)u1 * (double)u1) + (double)u2 * (double)u2;
-        r0.x = u0; r0.y = u1; r0.z = u2;
-        xb[0] = r0;
-      }
-      xo[0] = r0; xo[1] = r1; xo[2] = r2;
       s3[0] = r0.x; s3[1] = r0.y; s3[2] = r0.z;
     }
-    d2 = sw_wave_sum(d2);
-    n2 = sw_wave_sum(n2);
+    d2 = gfv_wave_sum(d2);
+    n2 = gfv_wave_sum(n2);
     if (lane == 0) {
       A.partial[2 * (size_t)c] = d2;
       A.partial[2 * (size_t)c + 1] = n2;
     }
   }
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(A.state + 1, 1) == (int)gridDim.x - 1;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
+  if (!gfv_arrive_last_all_fence(A.state + 1)) return;
   const float tol = A.ctl->tol;
   const int min_steps = A.ctl->min_steps, max_steps = A.ctl->max_steps, patience = A.ctl->patience;
   for (int b = wave; b < A.B; b += SW_WAVES) {
@@ -99,13 +72,9 @@ __global__ __launch_bounds__(64 * SW_WAVES) void sweep_advance_kernel(const Swee
     int age = s[0], streak = s[1], done = s[2];
     if (done == 0) {
       const int c0 = A.gchunk_ptr[b], c1 = min(A.gchunk_ptr[b + 1], A.n_chunks);
-      double d2 = 0.0, n2 = 0.0;
-      for (int q = c0 + lane; q < c1; q += 64) {
-        d2 += __hip_atomic_load(A.partial + 2 * (size_t)q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        n2 += __hip_atomic_load(A.partial + 2 * (size_t)q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      d2 = sw_wave_sum(d2);
-      n2 = sw_wave_sum(n2);
+      double p[2];
+      gfv_fold_chunks(A.partial, c0, c1, lane, p);
+      const double d2 = gfv_wave_sum(p[0]), n2 = gfv_wave_sum(p[1]);
       const float dn = (float)sqrt(d2), un = (float)sqrt(n2);
       const float rel = dn / un;                 // (0 / 0 and x / 0: NaN and inf compare false)
       age += 1;
