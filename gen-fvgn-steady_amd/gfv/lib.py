@@ -270,6 +270,12 @@ _SIGNATURES = {
     "gfv_anderson_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_void_p]),
+    "gfv_sweep_anderson_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32] + [C.c_void_p] * 14),
+    "gfv_sweep_anderson_mix": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_double, C.c_int32] + [C.c_void_p] * 6),
+    "gfv_sweep_advance_aa": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_int32] + [C.c_void_p] * 10),
     "gfv_trans_mlp_fwd": (C.c_int, [C.POINTER(TransMlp), C.c_void_p]),
     "gfv_trans_mlp_bwd": (C.c_int, [C.POINTER(TransMlpBwd), C.c_void_p]),
     "gfv_trans_mlp_ln_rows": (C.c_int, [C.c_int32]),

@@ -24,6 +24,15 @@ for its lifetime, never reallocated: `ctl`, `slots`, `last`, `state3`, the reduc
 A swap (the mirror shows a retired slot and something is pending): synchronise; read `slots` / `last` from device memory; pay
 `state3` back into ALL current entries; record the retired entries' results; load the new index list; zero the swapped slots.
 The mirror is only a hint that a synchronisation is worth it - every value acted on is read from device memory after it.
+
+Anderson acceleration per slot (`anderson=m`, 1 .. 8; gfv/anderson.py SlotAndersonState): for STEADY cases.
+Two more launches between the forward and the advance mix each live slot's model output with that slot's last m residual
+differences, decided on the device; the rings are per slot at a fixed stride (the largest node count of the pool at
+construction), the step index is the slot's own age, and a swap zeroes the swapped slots' state words.  The criterion is then the
+true fixed-point residual || G(x) - x || / || G(x) || (`rel_update` of a result is that of the latching step), and a step whose
+residual is below `tol` is a plain step: a converged entry's field is the model's own output G(x_k) with a measured residual
+below `tol`, the same guarantee as without it.  `anderson_stats()` reports, per entry of the last run, the accelerated steps, the
+restarts by kind and the depth of the last step.  `anderson=0` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -34,6 +43,7 @@ import struct
 
 import torch
 
+from . import anderson as AA
 from . import lib as L
 from . import listcache
 from .functions import require_gpu
@@ -108,9 +118,11 @@ class Sweep:
     WARM, EVICT_MAX = listcache.WARM, listcache.EVICT_MAX
 
     def __init__(self, model, pool, max_graphs=8, tol=1e-6, max_steps=40000, min_steps=1, patience=1, max_ahead=64,
-                 launch_mode="cmd_list", max_list_bytes=16 << 30, max_sizes=None):
+                 launch_mode="cmd_list", max_list_bytes=16 << 30, max_sizes=None, anderson=0, anderson_beta=1.0,
+                 anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0):
         if launch_mode not in ("cmd_list", "eager"):
             raise ValueError('launch_mode must be "cmd_list" or "eager"')
+        aa_args = AA.check_args(anderson, anderson_beta, anderson_reg, anderson_restart, anderson_start)
         self.max_steps = check_max_steps(max_steps)
         if int(min_steps) < 0 or int(patience) < 1 or int(max_ahead) < 0:
             raise ValueError("Sweep: min_steps >= 0, patience >= 1 and max_ahead >= 0 are required")
@@ -142,6 +154,12 @@ class Sweep:
         self._lists = listcache.ListCache(self.max_list_bytes, dev=dev)      # batch signature -> the recorded step
         self._counts = dict(steps=0, swaps=0)
         self._fwd = StaticForward(model, B, dev)
+        # Anderson acceleration per slot: rings at a fixed stride per slot, created once (recorded lists point at them)
+        self.anderson = aa_args[0]
+        self._aa, self._aa_stats = None, None
+        if self.anderson:
+            stride = max(int(sz["n"]) for sz in pool.sizes)
+            self._aa = AA.SlotAndersonState(B, stride, max(cap["nchunk"], 1), dev, *aa_args)
 
     def __del__(self):
         host = getattr(self, "_mirror", None)
@@ -169,11 +187,14 @@ class Sweep:
     def _body(self, graphs, pl):
         x, x_raw = graphs[0].x, graphs[0]._gfv_x_raw
         losses, uvp_node, _ = self._fwd.forward(x, x_raw, pl, False, self.norm_global)
-        L.check(L.load().gfv_sweep_advance(
-            uvp_node.data_ptr(), x_raw.data_ptr(), x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(), pl.chunk_end.data_ptr(),
-            pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(), self._ctl.data_ptr(),
-            self._slots.data_ptr(), self._last.data_ptr(), self._state3.data_ptr(), self._mirror_dev, self._state.data_ptr(),
-            L.stream_ptr()), "gfv_sweep_advance")
+        args = (uvp_node.data_ptr(), x_raw.data_ptr(), x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(), pl.chunk_end.data_ptr(),
+                pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(), self._ctl.data_ptr(),
+                self._slots.data_ptr(), self._last.data_ptr(), self._state3.data_ptr(), self._mirror_dev, self._state.data_ptr())
+        if self._aa is None:
+            L.check(L.load().gfv_sweep_advance(*args, L.stream_ptr()), "gfv_sweep_advance")
+        else:
+            self._aa.launch(uvp_node, x_raw, pl, self._ctl, self._slots)
+            L.check(L.load().gfv_sweep_advance_aa(*args, self._aa.aa_slot.data_ptr(), L.stream_ptr()), "gfv_sweep_advance_aa")
         L.status_publish()
         return losses, uvp_node
 
@@ -188,9 +209,22 @@ class Sweep:
         self._ctl.copy_(torch.tensor(words, dtype=torch.int32))
 
     def _read_slots(self):
-        """(synchronises) -> slots [B,4] and last [B,6] as the device holds them."""
+        """(synchronises) -> slots [B,4] and last [B,6] as the device holds them; with Anderson acceleration the per-slot counts
+        and records are copied at the same synchronisation."""
         torch.cuda.current_stream().synchronize()
+        if self._aa is not None:
+            self._aa_rows = (self._aa.aa_count.cpu(), self._aa.aa_slot.cpu())
         return self._slots.cpu(), self._last.cpu()
+
+    def anderson_stats(self):
+        """One dict per entry of the last `run`, in the order of its `entries`: {"accelerated": steps that were mixed,
+        "restarts": {"NONFINITE", "GROWTH", "SINGULAR"}, "last_depth": the depth of the entry's last step}.  Harvested where the
+        results are: no synchronisation of its own."""
+        if self._aa is None:
+            raise RuntimeError("this Sweep was built with anderson=0")
+        if self._aa_stats is None:
+            raise RuntimeError("anderson_stats() reports the last run(): nothing has run")
+        return list(self._aa_stats)
 
     @staticmethod
     def _result(entry, slot_row, last_row):
@@ -205,6 +239,9 @@ class Sweep:
         ents = check_entries(entries, self.pool.n)
         check_normalizer(self.model)
         self._fwd.check("Sweep", "sweep")
+        if self._aa is not None:
+            AA.check_ring_stride({e: self.pool.sizes[e]["n"] for e in ents}, self._aa.ring_stride)
+            self._aa_stats = []
         if not ents:
             return []
         sched = SlotScheduler(ents, lambda e: self.arena.signature([e])[0], self.arena.max_graphs)
@@ -218,6 +255,9 @@ class Sweep:
         self._slots.zero_()
         self._last.zero_()
         self._state.zero_()
+        if self._aa is not None:
+            self._aa.reset()
+        aa_stats = {}
         graphs, pl = self.arena.load(cur)
         key = sched.batch_signature()
         state3 = self._state3[:pl.N]
@@ -257,6 +297,8 @@ class Sweep:
             for b in done:
                 if b not in harvested:
                     results[cur[b]] = self._result(cur[b], slots[b], last[b])
+                    if self._aa is not None:
+                        aa_stats[cur[b]] = AA.count_dict(self._aa_rows[0][b], self._aa_rows[1][b])
                     harvested.add(b)
             new = sched.replace(done)
             if not new:
@@ -270,6 +312,8 @@ class Sweep:
             state3 = self._state3[:pl.N]
             for b in new:
                 self._slots[b].zero_()
+                if self._aa is not None:
+                    self._aa.reset_slot(b)
                 self._mirror[1 + 2 * b] = 0
                 self._mirror[2 + 2 * b] = 0
                 harvested.discard(b)
@@ -277,4 +321,6 @@ class Sweep:
         stream.synchronize()
         L.raise_on_status("Sweep.run")
         self._current = (key, graphs, pl)     # (what the arena holds: every slot frozen)
+        if self._aa is not None:
+            self._aa_stats = [aa_stats[e] for e in ents]
         return [results[e] for e in ents]

@@ -1034,6 +1034,45 @@ int gfv_anderson_mix(float* uvp_node, const float* f_cur, int32_t N, const int32
                      const float* dG, const double* gamma, const float* aa_table, int32_t K_max, const int32_t* step, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Anderson acceleration per slot of a sweep (gfv/sweep.py `Sweep(..., anderson=m)`, gfv/anderson.py SlotAndersonState; DESIGN.md
+ * 5e, 5k): the SLOT form of the two launches above, between the forward-only step and gfv_sweep_advance_aa.  The arithmetic, the
+ * summation order, the decision and the mix are those of gfv_anderson_gram / gfv_anderson_mix (one shared kernel body,
+ * csrc/anderson_kernel.h); what differs:
+ *   rings      a ring row of node i of slot b is  b * ring_stride + (i - chunk_beg[gchunk_ptr[b]])  - the node's index inside its
+ *              own graph, in the slot's own region: f_prev, g_prev [B * ring_stride, 3], dF, dG [m][B * ring_stride, 3].  A swap
+ *              of a neighbour to an entry of another size moves nothing under a live slot's columns.  ring_stride >= the node
+ *              count of every graph that ever runs (the host checks; a node beyond it is not touched).
+ *   step index the k compared with `start` is the slot's own age, slots[b, 0] (gfv_sweep_advance_aa increments it afterwards).
+ *   frozen     a slot with slots[b, 2] (done) != 0 when the launch starts is skipped entirely: none of its rings, state words,
+ *              gamma or records changes, and the mix writes none of its rows.
+ *   below tol  after decisions 1 and 2: when the fp32 quotient (float)|| f || / (float)|| g || - formed exactly as
+ *              gfv_sweep_advance_aa forms rel - is below ctl.tol (ctl: the 16 bytes of gfv_sweep_advance), the depth is 0 and the
+ *              column is kept.  A step that can latch therefore always advances to the model's own output G(x_k).
+ *   records    aa_slot [B, 4] float = (|| f ||, || g ||, depth, flags) of the slot's last live step (it stands where
+ *              aa_table[k, b] stands above; the mix reads its depth);  aa_count [B, 4] int32 += (depth > 0, NONFINITE, GROWTH,
+ *              SINGULAR) per live step.  The host zeroes aa_state[b], r_prev[b] and aa_count[b] when slot b takes a new entry;
+ *              rings need no clearing (cnt = 0 and has_prev = 0 mask them; stale values, NaN included, are never read).
+ * gfv_sweep_advance_aa is gfv_sweep_advance with rel = aa_slot[b, 0] / aa_slot[b, 1] (the true fixed-point residual
+ * || G(x) - x || / || G(x) ||, not the norm of the possibly mixed update it applied) and last[b, 4:6] = those two values;
+ * age, streak, patience, min / max steps, freeze, state3 and the mirror are as there.  partial_ws is not used by it but must be
+ * given (one signature, one check).
+ * GFV_ERR_ARG - before anything touches a device, nothing launched - as for the rollout form, and on ring_stride < 1.
+ * ---------------------------------------------------------------------------------------------------------- */
+int gfv_sweep_anderson_gram(const float* uvp_node, const float* x_backup, int32_t N, const int32_t* chunk_beg,
+                            const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, int32_t m, double reg,
+                            double restart, int32_t start, int32_t ring_stride, float* f_prev, float* g_prev, float* dF, float* dG,
+                            int32_t* aa_state, double* r_prev, double* gamma, double* partial_ws, int32_t* counter, const void* ctl,
+                            const int32_t* slots, float* aa_slot, int32_t* aa_count, void* stream);
+int gfv_sweep_anderson_mix(float* uvp_node, const float* f_cur, int32_t N, const int32_t* chunk_beg, const int32_t* chunk_end,
+                           const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, int32_t m, double beta, int32_t ring_stride,
+                           const float* dF, const float* dG, const double* gamma, const int32_t* slots, const float* aa_slot,
+                           void* stream);
+int gfv_sweep_advance_aa(const float* uvp_node, float* x_backup, float* x, int32_t N, const int32_t* chunk_beg,
+                         const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* losses,
+                         double* partial_ws, const void* ctl, int32_t* slots, float* last, float* state3, int32_t* mirror_dev,
+                         int32_t* state, const float* aa_slot, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Pool training (gfv/pool.py BatchArena, gfv/pool_trainer.py; the changing-batch loop of pre_train_Adam.py:112-198 with
  * Data_Pool.payback, Graph_loader.py:370-396): a batch of ANY entries of the device-resident pool assembled into FIXED memory
  * by one launch, and the prediction written back by one launch.
