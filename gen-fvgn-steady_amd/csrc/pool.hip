@@ -6,6 +6,9 @@
 // quads of that DESTINATION range, so the grid follows the bytes moved and every store is an aligned 16-byte store whatever word
 // a piece starts at.  The piece starts and the index offsets of the batch are a prefix sum over the B entries, formed by every
 // workgroup for its own attribute from the device-resident table (B <= 64 loads); the entry indices travel by value.
+//
+// Renewal (gfv/pool.py DevicePool.renew; Data_Pool.reset_env -> init_env, Graph_loader.py:154-229, Load_mesh.py:80-131): the
+// boundary conditions of K entries re-drawn and their fields restarted by one elementwise launch, the K records by value.
 #include "../../include/gfv.h"
 #include "gfv_common.h"
 #include "gfv_launch.h"
@@ -183,6 +186,88 @@ __global__ __launch_bounds__(256) void pool_payback_kernel(const PaybackK K) {
   }
 }
 
+// Renewal.  Elementwise: a workgroup owns RN_THREADS nodes of ONE entry (blk0: the first workgroup of every record), a thread one
+// node.  The float64 profile keeps the operation order of DevicePool.reset_env's torch expression - every torch op there is a
+// kernel of its own, so nothing is fused: contraction is off here whatever the build flags say.
+constexpr int RN_THREADS = 256;
+constexpr int NT_INFLOW = 1, NT_WALL = 3, NT_PRESS_POINT = 4, NT_IN_WALL = 5;   // NodeType (gfv/meshgen.py)
+
+struct RenewK {
+  gfv_renew_rec_t rec[MAXB];
+  int blk0[MAXB + 1];
+  int K;
+};
+
+#pragma clang fp contract(off)
+__device__ __forceinline__ void renew_profile(const gfv_renew_rec_t& r, int kind, double px, double py, double lo, double hi,
+                                              float& u, float& v, float& p) {
+  u = 0.0f; v = 0.0f; p = 0.0f;
+  switch (kind) {
+    case GFV_RENEW_PARABOLIC: {
+      const double yy = py - lo;
+      const double d = (hi - lo) - 0.0;        // (max - min of yy: min(yy) is py_min - py_min)
+      const double t1 = (6.0 * r.U) * yy;
+      const double t2 = d - yy;
+      const double t3 = d * d;
+      u = (float)(t1 * (t2 / t3));
+      break;
+    }
+    case GFV_RENEW_UNIFORM:
+      u = (float)r.U;
+      break;
+    case GFV_RENEW_UNIFORM_AOA:
+      u = (float)r.U * (float)r.cos_aoa;
+      v = (float)r.U * (float)r.sin_aoa;
+      break;
+    case GFV_RENEW_TAYLOR_GREEN: {
+      const double pi = 3.141592653589793;
+      const double ax = (2.0 * pi) * px, ay = (2.0 * pi) * py, bx = (4.0 * pi) * px, by = (4.0 * pi) * py;
+      u = (float)((r.U * sin(ax)) * cos(ay));
+      v = (float)(((-r.U) * cos(ax)) * sin(ay));
+      p = (float)(((-0.25) * r.U) * (cos(bx) + cos(by)));
+      break;
+    }
+    default: break;
+  }
+}
+
+__global__ __launch_bounds__(RN_THREADS) void pool_renew_kernel(const RenewK K) {
+  const int blk = blockIdx.x;
+  int lo = 0, hi = K.K;                        // the record of this workgroup: blk0[lo] <= blk < blk0[lo + 1]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (blk >= K.blk0[mid]) lo = mid; else hi = mid;
+  }
+  const gfv_renew_rec_t& r = K.rec[lo];
+  const int first = blk == K.blk0[lo];
+  const int i = (blk - K.blk0[lo]) * RN_THREADS + (int)threadIdx.x;
+  if (first && threadIdx.x < 13) {
+    const int t = threadIdx.x;
+    if (t < 9) r.theta[t] = r.coef[t];
+    else if (t == 9) r.dt[0] = r.coef[9];
+    else r.uvp_dim[t - 10] = r.coef[t];
+  }
+  if (i >= r.N) return;
+  const double px = r.pos[2 * (size_t)i], py = r.pos[2 * (size_t)i + 1];
+  const int nt = r.node_type[i];
+  float u, v, p;
+  renew_profile(r, r.init_kind, px, py, r.yrange[0], r.yrange[1], u, v, p);
+  if (nt == NT_INFLOW || nt == NT_IN_WALL || nt == NT_PRESS_POINT) {
+    float pi_;                                 // (the inlet call's pressure is not used: Load_mesh.py:109-118)
+    renew_profile(r, r.inlet_kind, px, py, r.yrange[2], r.yrange[3], u, v, pi_);
+  }
+  if (nt == NT_WALL) { u = 0.0f; v = 0.0f; }
+  if (nt == NT_IN_WALL) { u = u / 2.0f; v = v / 2.0f; p = p / 2.0f; }
+  const float inv_u = 1.0f / (float)r.U;
+  float* y = r.y + 2 * (size_t)i;
+  y[0] = u * inv_u;
+  y[1] = v * inv_u;
+  float* x = r.x + 12 * (size_t)i;
+  x[0] = u; x[1] = v; x[2] = p;
+#pragma unroll
+  for (int c = 0; c < 9; ++c) x[3 + c] = r.coef[c];
+}
+
 // what both entry points check of (table, batch) on the host
 bool pool_batch_ok(const int64_t* table_host, const int64_t* table_dev, int32_t n_entries, int32_t n_attrs, const int32_t* idx,
                    int32_t B) {
@@ -295,6 +380,34 @@ extern "C" int gfv_pool_payback(const int64_t* table_host, const int64_t* table_
   long wgs = (N + 255) / 256;
   if (wgs > 2048) wgs = 2048;
   GFV_LAUNCH(pool_payback_kernel, dim3((unsigned)wgs), dim3(256), 0, (hipStream_t)stream, K);
+  GFV_CHECK_LAUNCH();
+  return GFV_OK;
+}
+
+extern "C" int gfv_pool_renew(const gfv_renew_rec_t* recs, int32_t K, void* stream) {
+  if (!recs || K < 1 || K > MAXB) return GFV_ERR_ARG;
+  RenewK R;
+  long long blocks = 0;
+  double bytes = 0.0;
+  for (int k = 0; k < K; ++k) {
+    const gfv_renew_rec_t& r = recs[k];
+    if (!r.x || !r.y || !r.theta || !r.dt || !r.uvp_dim || !r.node_type || !r.pos || !r.yrange) return GFV_ERR_ARG;
+    if (r.N < 1 || r.U == 0.0 || !(r.U - r.U == 0.0)) return GFV_ERR_ARG;      // (U - U != 0: infinite or NaN)
+    if (r.inlet_kind < GFV_RENEW_NONE || r.inlet_kind > GFV_RENEW_TAYLOR_GREEN) return GFV_ERR_ARG;
+    if (r.init_kind < GFV_RENEW_NONE || r.init_kind > GFV_RENEW_TAYLOR_GREEN) return GFV_ERR_ARG;
+    for (int j = 0; j < k; ++j)
+      if (recs[j].x == r.x) return GFV_ERR_ARG;                                 // one writer per entry
+    R.rec[k] = r;
+    R.blk0[k] = (int)blocks;
+    blocks += (r.N + RN_THREADS - 1) / RN_THREADS;
+    bytes += (16.0 + 4.0 + 48.0 + 8.0) * (double)r.N;
+  }
+  if (blocks > 0x7fffffffLL) return GFV_ERR_ARG;
+  for (int k = K; k < MAXB; ++k) { R.rec[k] = recs[0]; R.blk0[k] = (int)blocks; }
+  R.blk0[MAXB] = (int)blocks;
+  R.K = K;
+  GfvProfScope ps_(GFV_K_MISC, 0, bytes, stream);
+  GFV_LAUNCH(pool_renew_kernel, dim3((unsigned)blocks), dim3(RN_THREADS), 0, (hipStream_t)stream, R);
   GFV_CHECK_LAUNCH();
   return GFV_OK;
 }

@@ -615,6 +615,7 @@ extern "C" int gfv_struct_size(int32_t which) {
     case 7: return (int)sizeof(gfv_trans_mlp_t);
     case 8: return (int)sizeof(gfv_trans_mlp_bwd_t);
     case 9: return (int)sizeof(gfv_fvm_mesh_t);
+    case 10: return (int)sizeof(gfv_renew_rec_t);
     default: return -1;
   }
 }

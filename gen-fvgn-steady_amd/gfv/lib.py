@@ -118,9 +118,21 @@ class PoolArgs(C.Structure):
                 ("reserved", C.c_int32), ("idx", C.c_int32 * POOL_MAX_GRAPHS)]
 
 
+RENEW_KINDS = {None: 0, "parabolic": 1, "uniform": 2, "uniform_aoa": 3, "Taylor_Green": 4}   # GFV_RENEW_* of include/gfv.h
+
+
+class RenewRec(C.Structure):
+    """gfv_renew_rec_t (include/gfv.h): one entry of a gfv_pool_renew launch."""
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("theta", C.c_void_p), ("dt", C.c_void_p), ("uvp_dim", C.c_void_p),
+                ("node_type", C.c_void_p), ("pos", C.c_void_p), ("yrange", C.c_void_p), ("U", C.c_double), ("cos_aoa", C.c_double),
+                ("sin_aoa", C.c_double), ("coef", C.c_float * 13), ("N", C.c_int32), ("inlet_kind", C.c_int32),
+                ("init_kind", C.c_int32)]
+
+
 _lib = None
 
 _SIGNATURES = {
+    "gfv_pool_renew": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
     "gfv_pool_args_bytes": (C.c_size_t, []),
     "gfv_pool_table_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "gfv_pool_table_check": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -347,7 +359,8 @@ def load(raw=False):
     if lib.gfv_abi_version() != ABI_VERSION:
         raise RuntimeError(f"libgfv.so has ABI {lib.gfv_abi_version()}, this binding is written for {ABI_VERSION}: rebuild it "
                            "(python gen-fvgn-steady_amd/gfv/build.py)")
-    for which, st in enumerate((Seg, Layer, RowtileArgs, WimgDesc, DwTile, ReducePiece, PlanDesc, TransMlp, TransMlpBwd, FvmMesh)):
+    for which, st in enumerate((Seg, Layer, RowtileArgs, WimgDesc, DwTile, ReducePiece, PlanDesc, TransMlp, TransMlpBwd, FvmMesh,
+                                RenewRec)):
         if lib.gfv_struct_size(which) != C.sizeof(st):
             raise RuntimeError(f"libgfv.so: struct {st.__name__} is {lib.gfv_struct_size(which)} bytes in the library, "
                                f"{C.sizeof(st)} in the binding")

@@ -398,19 +398,31 @@ def wlsq_moments(pos, face_node_x, support_edge, order="2nd"):
     return A, B[:ex], B[2 * ex:]
 
 
-def velocity_profile(pos, mean_u, kind):
-    uv = np.zeros_like(pos)
+def velocity_profile(pos, mean_u, kind, aoa=0.0, pressure=False):
+    """(u, v) [N, 2] of a profile kind of the reference's velocity_profile (Set_BC.py:6-66) at the positions `pos`, in float64;
+    pressure=True: -> (uv, p [N]), the pressure field the kind defines (zero for all but Taylor_Green).  aoa in degrees."""
+    uv, p = np.zeros_like(pos), np.zeros(pos.shape[0], dtype=pos.dtype)
     if pos.shape[0] == 0:
-        return uv
-    if kind == "parabolic":
+        pass
+    elif kind == "parabolic":
         y = pos[:, 1] - pos[:, 1].min()
         ymax, ymin = y.max(), y.min()
         uv[:, 0] = 6 * mean_u * y * (((ymax - ymin) - y) / (ymax - ymin) ** 2)
     elif kind == "uniform":
         uv[:, 0] = mean_u
-    else:
+    elif kind == "uniform_aoa":
+        # the reference forms U * (cos, sin) through a default-dtype (fp32) tensor, the angle read from an fp32 tensor
+        a = math.radians(float(np.float32(aoa)))
+        uv[:, 0] = np.float32(mean_u) * np.float32(math.cos(a))
+        uv[:, 1] = np.float32(mean_u) * np.float32(math.sin(a))
+    elif kind == "Taylor_Green":
+        x, y = pos[:, 0], pos[:, 1]
+        uv[:, 0] = mean_u * np.sin(2 * np.pi * x) * np.cos(2 * np.pi * y)
+        uv[:, 1] = -mean_u * np.cos(2 * np.pi * x) * np.sin(2 * np.pi * y)
+        p = -(1 / 4) * mean_u * (np.cos(4 * np.pi * x) + np.cos(4 * np.pi * y))
+    elif kind is not None:                      # None: no inlet velocity (zeros)
         raise ValueError(kind)
-    return uv
+    return (uv, p) if pressure else uv
 
 
 def pde_coefficients(bc):
@@ -456,10 +468,15 @@ def finish_mesh(raw, U=None, device=None, order="2nd"):
     Uin = float(bc["U"])
     nt = mesh["node|node_type"]
     inlet = (nt == INFLOW) | (nt == IN_WALL) | (nt == PRESS_POINT)
-    uv = velocity_profile(pos, Uin, bc["inlet_type"]).astype(np.float32)
-    uv[inlet] = velocity_profile(pos[inlet], Uin, bc["inlet_type"]).astype(np.float32)
+    # init_env (Load_mesh.py:80-131): the field starts from `init_field_type` (absent: the inlet kind), the inlet targets come
+    # from `inlet_type`; IN_WALL nodes carry half of (u, v, p)
+    aoa = float(bc.get("aoa", 0.0))
+    uv, p0 = velocity_profile(pos, Uin, bc.get("init_field_type", bc["inlet_type"]), aoa, pressure=True)
+    uv, p0 = uv.astype(np.float32), p0.astype(np.float32)
+    uv[inlet] = velocity_profile(pos[inlet], Uin, bc["inlet_type"], aoa).astype(np.float32)
     uv[nt == WALL] = 0
     uv[nt == IN_WALL] = uv[nt == IN_WALL] / 2.0
+    p0[nt == IN_WALL] = p0[nt == IN_WALL] / 2.0
     mesh.update({
         "face_node_x": face_node_x, "support_edge": support_edge,
         "A_node_to_node": A.astype(np.float32), "single_B_node_to_node": B1.astype(np.float32),
@@ -467,7 +484,7 @@ def finish_mesh(raw, U=None, device=None, order="2nd"):
         "theta_PDE": theta, "dt_graph": dt_graph, "uvp_dim": uvp_dim,
         "sigma": np.array([bc["sigma"]], dtype=np.float32), "bc": bc,
         "target|uvp": (uv / np.float32(Uin)).astype(np.float32),
-        "init_uvp": np.concatenate((uv, np.zeros((n_nodes, 1), np.float32)), axis=1),
+        "init_uvp": np.concatenate((uv, p0[:, None]), axis=1),
     })
     mesh.pop("face_node_x_base")
     return mesh

@@ -12,10 +12,13 @@ tensor-for-tensor equal to ``build_plan(build_batch(meshes))`` (tests/test_pool_
 For training over the pool with a new batch every step there is ``DevicePool.arena`` -> ``BatchArena``: the same batch, assembled
 into FIXED memory by one launch of ``gfv_pool_assemble`` with no per-step allocation or host-built table (what
 ``gfv.pool_trainer.PoolTrainStep`` replays recorded steps over), and ``DevicePool.add_variant``: entries that share a topology.
+``DevicePool.renew`` re-draws the boundary conditions of many entries by one launch (``gfv_pool_renew``; the reference's renewal
+schedule around it: ``gfv.renew.PoolRenewal``); ``reset_env`` is the same for one entry with torch ops.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -274,6 +277,10 @@ class DevicePool:
                             np.array([t.numel() for t in ts], dtype=np.int64), tuple(ts[0].shape[1:]), ts[0].dtype)
         self._src["x"] = (np.array([t.data_ptr() for t in self.x], dtype=np.uint64),
                           np.array([t.numel() for t in self.x], dtype=np.int64), tuple(self.x[0].shape[1:]), torch.float32)
+        # renew: min / max of pos[:, 1] over all nodes and over the inlet nodes, one row per topology (a variant shares the
+        # positions of its parent, and with them the row), reduced on the first renewal that touches the topology
+        self._yrange = torch.empty((max(self.n, 1), 4), dtype=torch.float64, device=self.device)
+        self._yrange_row = {}
 
     # ------------------------------------------------------------------------------------------------------------
     def batch(self, indices):
@@ -400,6 +407,82 @@ class DevicePool:
         x[:, 3:12] = p.theta
         p.y[:, 0] = u / np.float32(U)
         p.y[:, 1] = 0.0
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _yrange_ptr(self, i):
+        """Device address of entry i's row of the y-range table [min, max of pos[:, 1] over all nodes | over the inlet nodes];
+        the row is reduced when its topology is first asked for (reductions that do not synchronise; no inlet node: +inf, -inf)."""
+        from . import meshgen
+        key = self.pos64[i].data_ptr()
+        r = self._yrange_row.get(key)
+        if r is None:
+            r = len(self._yrange_row)
+            y, nt = self.pos64[i][:, 1], self.plans[i].node_type
+            other = ~((nt == meshgen.INFLOW) | (nt == meshgen.IN_WALL) | (nt == meshgen.PRESS_POINT))
+            self._yrange[r].copy_(torch.stack((y.amin(), y.amax(), y.masked_fill(other, float("inf")).amin(),
+                                               y.masked_fill(other, float("-inf")).amax())))
+            self._yrange_row[key] = r
+        return self._yrange.data_ptr() + 32 * r
+
+    @staticmethod
+    def _renew_kind(v, what):
+        if v is not None and not isinstance(v, str):
+            raise ValueError(f"{what}: the list-valued form ([u, v, p]) is not implemented (nor is it by the reference's velocity_profile)")
+        if v not in L.RENEW_KINDS:
+            if v.lower().endswith((".vtu", ".h5")):
+                raise ValueError(f"{what}: the file-valued form ('{v}') is not implemented (nor is it by the reference's velocity_profile)")
+            raise ValueError(f"{what}: unknown profile kind '{v}' (known: {[k for k in L.RENEW_KINDS if k]} and None)")
+        return L.RENEW_KINDS[v]
+
+    def renew(self, indices, sampled):
+        """`reset_env` for many entries at once: ONE launch of gfv_pool_renew per POOL_MAX_GRAPHS entries, no host synchronisation,
+        nothing uploaded (the records - pointers, the 13 coefficients, U, the angle - travel in the launch's arguments).
+        sampled: one dict per index with the keys of `reset_env` (U, rho, mu, source, aoa, dt, L) and optionally `inlet_type` /
+        `init_field_type`: a profile kind of the reference's velocity_profile (Set_BC.py:33-64: "parabolic", "uniform",
+        "uniform_aoa", "Taylor_Green", None).  The initial field follows `init_field_type` (absent: the inlet kind), the Dirichlet
+        targets `inlet_type` (Load_mesh.py:86-118); the host-side `bc` records are updated as `reset_env` updates them.  ValueError
+        - nothing changed - for an entry without a `bc` record, an unknown kind, a repeated index, or U = 0."""
+        from . import meshgen
+        idx = [int(i) for i in indices]
+        sampled = list(sampled)
+        if len(sampled) != len(idx):
+            raise ValueError(f"{len(idx)} entries but {len(sampled)} sets of sampled values")
+        if len(set(idx)) != len(idx):
+            raise ValueError("an entry is given twice in one renewal")
+        new_bc, recs = [], (L.RenewRec * max(len(idx), 1))()
+        for k, (i, s) in enumerate(zip(idx, sampled)):
+            if not 0 <= i < self.n:
+                raise ValueError(f"pool entry {i} does not exist (the pool holds {self.n})")
+            if self.bc[i] is None:
+                raise ValueError("the mesh was given without its 'bc' record (gfv.meshgen.finish_mesh keeps it)")
+            bc = dict(self.bc[i])
+            for key, v in s.items():
+                bc[key] = v if key in ("inlet_type", "init_field_type") else float(v)
+            inlet_kind = self._renew_kind(bc["inlet_type"], "inlet_type")
+            init_kind = self._renew_kind(bc.get("init_field_type", bc["inlet_type"]), "init_field_type")
+            U = float(bc["U"])
+            if U == 0.0 or not math.isfinite(U):
+                raise ValueError("the inlet velocity U must be finite and non-zero (everything is made dimensionless by it)")
+            theta, dt_graph, uvp_dim = meshgen.pde_coefficients(bc)
+            p, r = self.plans[i], recs[k]
+            r.x, r.y, r.theta, r.dt, r.uvp_dim = (t.data_ptr() for t in (self.x[i], p.y, p.theta, p.dt, p.uvp_dim))
+            r.node_type, r.pos, r.N = p.node_type.data_ptr(), self.pos64[i].data_ptr(), int(self.x[i].shape[0])
+            aoa = math.radians(float(np.float32(bc["aoa"])))    # (init_env reads the angle from the mesh's fp32 tensor)
+            r.U, r.cos_aoa, r.sin_aoa = U, math.cos(aoa), math.sin(aoa)
+            r.coef[:] = np.concatenate((theta.reshape(-1), dt_graph.reshape(-1), uvp_dim.reshape(-1))).tolist()
+            r.inlet_kind, r.init_kind = inlet_kind, init_kind
+            new_bc.append(bc)
+        for k, i in enumerate(idx):
+            recs[k].yrange = self._yrange_ptr(i)
+        lib, stream = L.load(), L.stream_ptr()
+        for k0 in range(0, len(idx), L.POOL_MAX_GRAPHS):
+            K = min(L.POOL_MAX_GRAPHS, len(idx) - k0)
+            rc = lib.gfv_pool_renew(C.addressof(recs) + k0 * C.sizeof(L.RenewRec), K, stream)
+            if rc == -1:
+                raise ValueError("gfv_pool_renew refused the records")
+            L.check(rc, "gfv_pool_renew")
+        for i, bc in zip(idx, new_bc):
+            self.bc[i].update(bc)
 
     # ------------------------------------------------------------------------------------------------------------
     def add_variant(self, i, fields=None, **sampled):

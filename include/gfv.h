@@ -37,7 +37,7 @@ extern "C" {
 int gfv_abi_version(void);
 /* sizeof of the argument structs as the library was compiled (which: 0 gfv_seg_t, 1 gfv_layer_t, 2 gfv_rowtile_args_t,
  * 3 gfv_wimg_desc_t, 4 gfv_dw_tile_t, 5 gfv_reduce_piece_t, 6 gfv_plan_desc_t, 7 gfv_trans_mlp_t, 8 gfv_trans_mlp_bwd_t,
- * 9 gfv_fvm_mesh_t): lets a
+ * 9 gfv_fvm_mesh_t, 10 gfv_renew_rec_t): lets a
  * binding check its own layout */
 int gfv_struct_size(int32_t which);
 
@@ -1128,6 +1128,40 @@ int gfv_pool_assemble(const gfv_pool_args_t* args, void* stream);
  * GFV_ERR_ARG as for gfv_pool_assemble, and for a NULL uvp_node, x_attr outside the table or a wrong N. */
 int gfv_pool_payback(const int64_t* table_host, const int64_t* table_dev, int32_t n_entries, int32_t n_attrs, int32_t x_attr,
                      const int32_t* idx, int32_t B, const float* uvp_node, int64_t N, float* raw, void* stream);
+
+/* Pool renewal (gfv/pool.py DevicePool.renew, gfv/renew.py; Data_Pool.reset_env -> transform_mesh -> init_env,
+ * Graph_loader.py:154-229,389-396, Load_mesh.py:80-131, Set_BC.py:6-66): the boundary condition of K entries re-drawn and their
+ * fields restarted by ONE launch.  The K records travel by value in the launch's argument block (as the indices of
+ * gfv_pool_assemble).  Per node of every entry, in init_env's order: (u, v, p) from the initial-field kind over all nodes; on
+ * INFLOW / IN_WALL / PRESS_POINT nodes (u, v) from the inlet kind; on WALL nodes (u, v) = 0; on IN_WALL nodes (u, v, p) halved;
+ * y = (u, v) * (1.0f / (float)U) (the reciprocal product torch forms for a division by a host scalar); x[:, 0:3] = (u, v, p),
+ * x[:, 3:12] = coef[0 .. 8].  One thread per entry writes theta = coef[0 .. 8], dt = coef[9], uvp_dim = coef[10 .. 12].
+ * Profile kinds (evaluated in float64 on pos, rounded to fp32; no contraction):
+ *   GFV_RENEW_NONE         zeros
+ *   GFV_RENEW_PARABOLIC    u = (6 U (py - lo)) * (((hi - lo) - (py - lo)) / ((hi - lo) * (hi - lo))), (lo, hi) = yrange[0 .. 1] for
+ *                          the initial field (all nodes), yrange[2 .. 3] for the inlet targets (inlet nodes)
+ *   GFV_RENEW_UNIFORM      u = U
+ *   GFV_RENEW_UNIFORM_AOA  (u, v) = (float)U * ((float)cos_aoa, (float)sin_aoa): fp32 products
+ *   GFV_RENEW_TAYLOR_GREEN u = U sin(2 pi x) cos(2 pi y), v = -U cos(2 pi x) sin(2 pi y), p = -(U / 4) (cos(4 pi x) + cos(4 pi y))
+ * yrange is DEVICE memory (it depends on geometry only; the caller reduces it once per topology); nothing else is read from the
+ * device but pos and node_type.  No reduction, no atomics, no LDS.
+ * GFV_ERR_ARG - before anything touches a device, nothing launched - on NULL records, K outside [1, GFV_POOL_MAX_GRAPHS], a NULL
+ * pointer inside a record, N < 1, an unknown kind, U == 0 or not finite, or two records with the same x (two blocks would race). */
+enum { GFV_RENEW_NONE = 0, GFV_RENEW_PARABOLIC = 1, GFV_RENEW_UNIFORM = 2, GFV_RENEW_UNIFORM_AOA = 3, GFV_RENEW_TAYLOR_GREEN = 4 };
+typedef struct {
+  float* x;                  /* [N, 12] */
+  float* y;                  /* [N, 2] */
+  float* theta;              /* [1, 9] */
+  float* dt;                 /* [1] */
+  float* uvp_dim;            /* [1, 3] */
+  const int32_t* node_type;  /* [N] */
+  const double* pos;         /* [N, 2] */
+  const double* yrange;      /* [4]: min, max of pos[:, 1] over all nodes; min, max over the inlet nodes (+inf, -inf: none) */
+  double U, cos_aoa, sin_aoa;
+  float coef[13];            /* theta_PDE [9] | dt_graph | uvp_dim [3] */
+  int32_t N, inlet_kind, init_kind;
+} gfv_renew_rec_t;           /* gfv_struct_size(10) */
+int gfv_pool_renew(const gfv_renew_rec_t* recs, int32_t K, void* stream);
 
 /* ----------------------------------------------------------------------------------------------------------
  * L-BFGS on flat fp32 vectors (csrc/lbfgs.hip; gfv/optim.py LBFGS): torch.optim.LBFGS's two-loop recursion carried out on
