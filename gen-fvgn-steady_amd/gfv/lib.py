@@ -106,6 +106,8 @@ class FvmMesh(C.Structure):
 
 POOL_MAX_GRAPHS, POOL_MAX_ATTRS, POOL_ROW_HEAD = 64, 56, 8   # GFV_POOL_* of include/gfv.h
 EVAL_RECORD = 16   # GFV_EVAL_RECORD of include/gfv.h: floats per row of the table gfv_eval_collect fills
+# GFV_TRAIN_LOG_* of include/gfv.h: logical elements per chunk, head words of a ring row, words per entry-table row, buckets at most
+TRAIN_LOG_CHUNK, TRAIN_LOG_HEAD, TRAIN_LOG_ENTRY_RECORD, TRAIN_LOG_MAX_BUCKETS = 1024, 16, 8, 32
 POOL_COPY, POOL_ADD, POOL_ROWPTR, POOL_FILL = 0, 1, 2, 3
 
 
@@ -276,6 +278,14 @@ _SIGNATURES = {
     "gfv_eval_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "gfv_train_log_chunks": (C.c_int64, [C.c_int64]),
+    "gfv_train_log_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gfv_train_log_row_words": (C.c_int32, [C.c_int32, C.c_int32]),
+    "gfv_train_log_norms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "gfv_train_log_append": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_void_p]),
     "gfv_anderson_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32,
                                     C.c_int32, C.c_double, C.c_double, C.c_int32] + [C.c_void_p] * 10 + [C.c_int32, C.c_void_p,
                                                                                                          C.c_void_p]),

@@ -48,6 +48,7 @@ from .groups import check_groups
 from .guard import check_policy
 from .static_forward import prep_scratch
 from .trainer import TrainStep
+from .trainlog import make_log
 
 _SCRATCH = ("_zero_e", "_dw_ws", "_dw_ws_main", "_prep_ws", "_fvm_cnt")
 _FIXED = ("_zero_e", "_prep_ws", "_fvm_cnt")       # sized once for the arena's capacity
@@ -59,7 +60,7 @@ class PoolTrainStep(TrainStep):
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
@@ -69,12 +70,13 @@ class PoolTrainStep(TrainStep):
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
+        log = make_log(log, self.arena.max_graphs)                  # (before anything is built: its arguments are checked here)
         graphs, _ = self.arena.load([0])
         super().__init__(model, graphs, lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, world_size=1, use_graph=use_graph,
                          want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
                          skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
                          ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
-                         decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups)
+                         decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, log=log)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = listcache.ListCache(self.max_list_bytes)     # key -> Entry with engine_sig, early, scratch
@@ -130,6 +132,9 @@ class PoolTrainStep(TrainStep):
     # ---- one step ------------------------------------------------------------------------------------------------------
     def step(self, indices, payback=False, advance=False):
         """One training iteration over the pool entries `indices` -> the (device) scalar loss tensor.
+        With `log=...` every call - every micro-step of an accumulation too, `apply` 0 on the hold ones - appends a row carrying
+        `indices` to `self.log` and updates its per-entry table; under data parallelism the log is rank-local (this rank's
+        loss and entries, the reduced gradient).
         payback: write the predicted (u, v, p) back into the entries' own `x` (one launch); advance: also into the arena's raw
         state, so that the next inner step over the SAME batch starts from it (`TrainStep.advance_time`)."""
         self._not_swapped("step()")
@@ -181,6 +186,7 @@ class PoolTrainStep(TrainStep):
             self.model.node_norm.note_accumulated()
         if self._accum is not None:
             self._accum.note_step()
+        self._log_step(idx, self.pool.n)     # (eager, behind Adam, outside the list: the row carries this step's entries)
         if payback or advance:
             if self.uvp_node is None:
                 raise RuntimeError("payback needs the prediction of the step (want_outputs=True)")

@@ -24,6 +24,7 @@ from .groups import ParamGroups, check_groups, check_weight_decay
 from .guard import GradGuard, check_policy
 from .optstep import optimizer_launches
 from .plan import _live_key, _refresh_live, get_plan
+from .trainlog import make_log
 
 
 def _gather(src, index, out):
@@ -34,7 +35,7 @@ class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None):
         # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
         # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
         dist_on = (world_size > 1) if distributed is None else bool(distributed)
@@ -101,9 +102,15 @@ class TrainStep:
         self._ema = WeightEMA(self.flat_p, total, ema_decay, self._ema_warmup) if ema_decay is not None else None
         # parameter groups (gfv/groups.py): None with everything at its default - no table, _adam() as it was
         self._graphs, self._list_warm = {}, {}
+        self.log = None
         spec.skip = set(self.G.skip)
         spec.check_some_live([g["frozen"] for g in spec.groups])
         self._groups_changed(frozen_changed=bool(spec.frozen_names()))
+        # training log (gfv/trainlog.py): None with log=None - no launch, no allocation.  An int capacity, a
+        # TrainLog or a dict of its arguments; its two launches follow every step eagerly (_log_step), outside lists and graphs
+        self.log = make_log(log, self.plan.B)
+        if self.log is not None:
+            self.log.bind(self.G, dev, spec.frozen_names(), owner=self)
         self.x = graphs[0].x
         self.x_backup = self.x.clone()
         B = self.plan.B
@@ -234,6 +241,8 @@ class TrainStep:
             frozen = gs.frozen_names()
             self._stateful |= self._live_names()
             self._guard.set_segments(self.G, frozen)
+            if self.log is not None:
+                self.log.set_buckets(self.G, frozen)     # (its launches are in no list: nothing more to drop)
             self._drop_recorded()
 
     def _live_names(self):
@@ -641,6 +650,17 @@ class TrainStep:
             self._allreduce()
             self._adam()
 
+    def _log_step(self, entries=None, n_entries=0):
+        """The training log's two launches (gfv/trainlog.py), eagerly on the current stream behind the optimiser launches of the
+        step - whichever way those were issued: eager, replayed from a list, replayed from a hipGraph, or behind the all-reduce.
+        Never recorded: `losses` differs per recorded list and the pool entries per step (the rule of Evaluate's collect
+        launch).  Under data parallelism the log is rank-local: this rank's loss and terms, the REDUCED gradient."""
+        if self.log is None:
+            return
+        self.log.append(self.flat_g, self.flat_p, self.adam_state, self.hyper, self.loss, self.losses, self.plan.B,
+                        guard=self._guard.guard if self._guard.active else None,
+                        accum=None if self._accum is None else self._accum.rec, entries=entries, n_entries=n_entries)
+
     def _check_aliasing(self):
         """The module's parameters must still be the views of the flat buffer this object made them (a `model.to()`, a
         `load_state_dict(assign=True)` or a second TrainStep on the same model re-points them): captured steps hold raw
@@ -654,7 +674,10 @@ class TrainStep:
 
     def step(self):
         """One training iteration.  Returns the (device) scalar loss tensor of this rank's batch.
-        `use_graph`: False = eager launches, True = hipGraph replay, "list" = command-list replay."""
+        `use_graph`: False = eager launches, True = hipGraph replay, "list" = command-list replay.
+        With `log=...` the step also appends one row to `self.log` (gfv/trainlog.py): read it with `ts.log.read()` when
+        convenient - nothing in step() waits for the device.  Under data parallelism the log is rank-local (this rank's loss,
+        the reduced gradient)."""
         self._not_swapped("step()")
         self._check_aliasing()
         # what the kernels of the steps BEFORE the last one raised in the device status word (a hidden activation outside the
@@ -739,6 +762,7 @@ class TrainStep:
             self.model.node_norm.note_accumulated()
         if self._accum is not None:
             self._accum.note_step()
+        self._log_step()
         return self.loss
 
     # state snapshot so the capture warm-up does not advance training ---------------------------------------

@@ -992,6 +992,67 @@ int gfv_eval_collect(const float* uvp_node, const float* x_raw, const float* tar
                      int32_t* counter, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Training log (gfv/trainlog.py): per-step losses, norms and guard decisions kept on the device.  Two launches,
+ * issued in this order behind the optimiser launches of a step (so every record they read is the one Adam left), eagerly in
+ * every launch mode and never inside a recorded list or a captured graph; the host reads the ring once per epoch.
+ *
+ * gfv_train_log_norms: ONE launch.  For each of K buckets: sum of g[i]^2, sum of p[i]^2 and the count of non-finite g[i] over
+ *   the bucket's elements, three doubles into sums [K, 3].  g is read as stored (no grad_scale, no clip coefficient).
+ *   segs: DEVICE table of (offset, count) int64 pairs into g and p, the format of the guard's table; bucket k owns the segments
+ *   bucket_tab[k][0] .. bucket_tab[k][1] - 1.  bucket_tab: DEVICE int64 [K, 4] = {first segment, one past the last segment,
+ *   first chunk, elements}: elements = the sum of the bucket's counts (at least 1), chunks are GFV_TRAIN_LOG_CHUNK logical
+ *   elements of one bucket, numbered bucket after bucket (first chunk of k + 1 = first chunk of k + its chunk count, what
+ *   gfv_train_log_chunks says of its element count); n_chunks = their total.  Nothing outside a segment is read.
+ *   Squares and sums in double, in a FIXED order defined over the logical index j of a bucket's concatenated elements - not over
+ *   the grid, timing or a segment's alignment - with no floating-point atomics:
+ *     chunk c of a bucket = elements 1024 c .. min(1024 (c + 1), n) - 1; lane l of one wave adds, from +0.0, the elements
+ *     1024 c + 256 r + 4 l + (0 .. 3) for r = 0 .. 3 in ascending order; the 64 lanes fold by xor butterfly, levels 32 .. 1;
+ *     the workgroup that arrives last folds a bucket's chunk sums: lane l adds chunks l, l + 64, ... ascending, same butterfly.
+ *   16-byte loads where four consecutive logical elements lie in one segment at a 16-byte aligned address, element loads
+ *   elsewhere: the same values in the same order.
+ *   workspace: gfv_train_log_workspace_bytes of n_chunks, 8-byte aligned, ZEROED once by the caller (first word: the arrival
+ *   counter, left at zero by every launch).  K == 0: GFV_OK, nothing launched, nothing written.
+ *   GFV_ERR_ARG (nothing launched) on K < 0 or above GFV_TRAIN_LOG_MAX_BUCKETS and, with K > 0, a NULL pointer (a NULL bucket
+ *   table included), n_chunks < 1 or a misaligned workspace.
+ *
+ * gfv_train_log_append: ONE workgroup.  Writes row (cursor mod capacity) of the ring and then cursor += 1; cursor is a DEVICE
+ *   64-bit count of all appends.  A row is gfv_train_log_row_words of (max_graphs, K) 32-bit words:
+ *     [0..1]  ordinal (int64)     the cursor before this append
+ *     [2]     adam_t              state[0]: optimiser steps completed, this one included
+ *     [3]     loss                loss[0], bit copy
+ *     [4]     lr                  hyper[0]
+ *     [5]     B (int32)           graph count of this call
+ *     [6] [7] [8]                 guard[2] norm, guard[3] coef, guard[4] decision (int32); guard == NULL: NaN, 1.0f, 0
+ *     [9]     apply (int32)       accum[3]; accum == NULL: 1
+ *     [10]    applied (int32)     1 if apply and the decision carries no skip bit, else 0
+ *     [11..15]                    zero
+ *     [16 .. 16 + 4 max_graphs)   terms: losses[B, 4] bit copies, rows B and beyond zero
+ *     then max_graphs int32       entries: the pool entry of every slot, -1 where there is none
+ *     (one zero word if 5 max_graphs is odd) then K x 3 doubles: sums of the norms launch
+ *   entry: HOST array of B int32 or NULL (none: every slot -1); it travels by value in the launch's argument block.
+ *   table: optional DEVICE int32 [n_entries, GFV_TRAIN_LOG_ENTRY_RECORD], updated for slot 0, 1, .. B - 1 in this order for every
+ *   entry >= 0 (the same entry twice counts two visits, the later slot's terms stay):
+ *     [0] visits (int32)  [1] ordinal of the last visit (int32, the low word)  [2..5] the four terms of the last visit  [6] [7] zero
+ *   GFV_ERR_ARG (nothing launched) on a NULL ring, cursor, state, hyper, loss or losses, capacity < 1, B outside [1, max_graphs],
+ *   max_graphs above GFV_POOL_MAX_GRAPHS, an entry outside [-1, n_entries) (without a table: below -1), K < 0 or above
+ *   GFV_TRAIN_LOG_MAX_BUCKETS, NULL sums with K > 0, a table with n_entries < 1, a ring or cursor that is not 8-byte aligned.
+ * gfv_train_log_row_words: GFV_ERR_ARG for a max_graphs outside [1, GFV_POOL_MAX_GRAPHS] or a K outside the range above.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_TRAIN_LOG_CHUNK 1024
+#define GFV_TRAIN_LOG_HEAD 16
+#define GFV_TRAIN_LOG_ENTRY_RECORD 8
+#define GFV_TRAIN_LOG_MAX_BUCKETS 32
+int64_t gfv_train_log_chunks(int64_t n_elems);
+size_t gfv_train_log_workspace_bytes(int64_t n_chunks);
+int32_t gfv_train_log_row_words(int32_t max_graphs, int32_t K);
+int gfv_train_log_norms(const float* g, const float* p, const int64_t* segs, const int64_t* bucket_tab, int32_t K, int64_t n_chunks,
+                        double* sums, void* workspace, void* stream);
+int gfv_train_log_append(void* ring, int32_t capacity, int32_t max_graphs, int32_t K, int64_t* cursor, const float* state,
+                         const float* hyper, const float* loss, const float* losses, int32_t B, const float* guard,
+                         const float* accum, const int32_t* entry, const double* sums, int32_t* table, int32_t n_entries,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Anderson acceleration AA(m) of the steady-state rollout (gfv/anderson.py, gfv/rollout.py): two launches between
  * the forward-only step and gfv_rollout_advance.  Per graph b over its node rows x 3 channels, fp32: x = x_backup[:, 0:3],
  * g = uvp_node, f = g - x.  State of the caller's, zero before the first step and never touched by anything else:
