@@ -760,7 +760,7 @@ __global__ __launch_bounds__(1024) void fvm_tail_kernel(const float* __restrict_
     for (int g = tid; g < B; g += 64) {
       const float l0 = gfv_ld_agent(losses + 4 * g), l1 = gfv_ld_agent(losses + 4 * g + 1);
       const float l2 = gfv_ld_agent(losses + 4 * g + 2), l3 = gfv_ld_agent(losses + 4 * g + 3);
-      const float tot = wp * l3 + wc * l0 + wm * l1 + wm * l2;
+      const float tot = gfv_weighted_residual(l0, l1, l2, l3, wc, wm, wp);
       s += logf(tot);
       const float inv = 1.0f / (tot * (float)B);
       gloss[4 * g] = wc * inv; gloss[4 * g + 1] = wm * inv; gloss[4 * g + 2] = wm * inv; gloss[4 * g + 3] = wp * inv;

@@ -170,6 +170,14 @@ static __device__ __forceinline__ float gfv_wave_min(float v) {
   return fminf(a, b);
 }
 
+// The weighted residual of one graph, w_p L_p + w_c L_c + w_m L_mx + w_m L_my (pre_train_Adam.py:177-184; l0 .. l3 = cont, mom_x,
+// mom_y, press): the argument of the training loss's logarithm (train_loss_kernel of csrc/misc.hip, the tail of the loss launch in csrc/fvm.hip) and the residual the
+// time march tests (csrc/march.hip).  ONE statement for all three, so that they cannot drift apart: fp32, every product and sum
+// rounded on its own, added left to right.
+static __device__ __forceinline__ float gfv_weighted_residual(float l0, float l1, float l2, float l3, float wc, float wm, float wp) {
+  return wp * l3 + wc * l0 + wm * l1 + wm * l2;
+}
+
 static inline int gfv_div_up(long a, long b) { return (int)((a + b - 1) / b); }
 
 // XCD-aware tile order.  The 256 CUs sit in 8 XCDs with one L2 each and the dispatcher deals consecutive workgroup ids

@@ -696,7 +696,7 @@ __global__ void train_loss_kernel(const float* __restrict__ losses, int B, float
   const int tid = threadIdx.x;
   float s = 0.f;
   for (int b = tid; b < B; b += 64) {
-    const float tot = wp * losses[4 * b + 3] + wc * losses[4 * b] + wm * losses[4 * b + 1] + wm * losses[4 * b + 2];
+    const float tot = gfv_weighted_residual(losses[4 * b], losses[4 * b + 1], losses[4 * b + 2], losses[4 * b + 3], wc, wm, wp);
     s += logf(tot);
     const float inv = 1.0f / (tot * (float)B);
     gloss[4 * b] = wc * inv; gloss[4 * b + 1] = wm * inv; gloss[4 * b + 2] = wm * inv; gloss[4 * b + 3] = wp * inv;

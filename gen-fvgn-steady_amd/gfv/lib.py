@@ -108,6 +108,8 @@ POOL_MAX_GRAPHS, POOL_MAX_ATTRS, POOL_ROW_HEAD = 64, 56, 8   # GFV_POOL_* of inc
 EVAL_RECORD = 16   # GFV_EVAL_RECORD of include/gfv.h: floats per row of the table gfv_eval_collect fills
 # GFV_TRAIN_LOG_* of include/gfv.h: logical elements per chunk, head words of a ring row, words per entry-table row, buckets at most
 TRAIN_LOG_CHUNK, TRAIN_LOG_HEAD, TRAIN_LOG_ENTRY_RECORD, TRAIN_LOG_MAX_BUCKETS = 1024, 16, 8, 32
+# GFV_MARCH_* of include/gfv.h: words of the march record, head words and per-graph words of a history row, the two flags
+MARCH_RECORD, MARCH_HEAD, MARCH_GRAPH, MARCH_CONVERGED, MARCH_CAPPED = 16, 8, 8, 1, 2
 POOL_COPY, POOL_ADD, POOL_ROWPTR, POOL_FILL = 0, 1, 2, 3
 
 
@@ -275,6 +277,9 @@ _SIGNATURES = {
     "gfv_sweep_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_void_p, C.c_void_p]),
+    "gfv_march_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                                                     C.c_void_p, C.c_void_p]),
     "gfv_eval_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

@@ -13,22 +13,32 @@ With A = accumulation on, G = guard active, E = averaged weights on, P = paramet
        G               gfv_adam_step_guarded_dev
        none of them    gfv_adam_step_dev
 
-The entry per form is fixed: it decides the kernel instantiation, and with it the bits of the step."""
+The entry per form is fixed: it decides the kernel instantiation, and with it the bits of the step.
+
+H = `hold` given (gfv/march.py): a device record whose word [3] is an apply flag that SOMEBODY ELSE's launch has
+written in front of these.  It goes where accum's record goes in 2 and 3 - the guard's `_accum` entry, the Adam entry as with A -
+and launch 1 is not issued: of that record the launches of 2 and 3 read word [3] alone (csrc/misc.hip AC_APPLY; include/gfv.h).
+With the flag at 1 their results are those of the forms without a record, bit for bit."""
 from __future__ import annotations
 
 from . import lib as L
 
 
-def optimizer_launches(p, g, m, v, n, state, hyper, *, guard=None, accum=None, ema=None, groups=None, B=1, loss=None):
+def optimizer_launches(p, g, m, v, n, state, hyper, *, guard=None, accum=None, ema=None, groups=None, B=1, loss=None, hold=None):
     """p, g, m, v: flat fp32 tensors of n elements; state, hyper: the Adam step record and the hyper-parameters; guard, accum,
     ema, groups: the record owners or None (a guard counts only when `.active`); B, loss: graph count and device loss of this
-    micro-batch, read by the accumulate launch only."""
+    micro-batch, read by the accumulate launch only; hold: a device tensor of at least 4 32-bit words, word [3] the apply flag
+    (not together with accum: the two would claim the same argument)."""
+    if hold is not None and accum is not None:
+        raise ValueError("optimizer_launches: hold= and accum= both name the record the Adam launch reads its apply flag from")
     lib, st = L.load(), L.stream_ptr()
     gp, hp = g.data_ptr(), hyper.data_ptr()
     arec = None
     if accum is not None:
         arec = accum.rec.data_ptr()
         L.check(lib.gfv_grad_accum_dev(gp, accum.acc.data_ptr(), n, int(B), loss.data_ptr(), arec, st), "grad_accum")
+    elif hold is not None:
+        arec = hold.data_ptr()
     grec = None
     if guard is not None and guard.active:
         grec = guard.guard.data_ptr()
@@ -46,7 +56,7 @@ def optimizer_launches(p, g, m, v, n, state, hyper, *, guard=None, accum=None, e
                 "adam_step_groups")
     elif ema is not None:
         L.check(lib.gfv_adam_step_ema_dev(*pmv, e, n, sp, hp, grec, arec, erec, st), "adam_step_ema")
-    elif accum is not None:
+    elif arec is not None:
         L.check(lib.gfv_adam_step_accum_dev(*pmv, n, sp, hp, grec, arec, st), "adam_step_accum")
     elif grec is not None:
         L.check(lib.gfv_adam_step_guarded_dev(*pmv, n, sp, hp, grec, st), "adam_step_guarded")

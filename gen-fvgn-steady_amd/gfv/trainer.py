@@ -579,8 +579,13 @@ class TrainStep:
         if self.padded:
             cmdlist.call(_gather, self.G_run.flat, self._unpad_map, self.flat_g)
         self.losses, self.uvp_node, self.uvp_cell = losses, uvp_node, uvp_cell
+        self._after_backward()
         if with_adam:
             self._adam()
+
+    def _after_backward(self):
+        """Launches of a subclass between the backward and the optimiser's (gfv.march.MarchStep: the march launch): part of the
+        step body, so eager steps, recorded lists and captures carry them alike.  Nothing here."""
 
     def _adam(self):
         """The optimiser step's one to three launches (gfv/optstep.py): eager, list and hipGraph mode all go through here."""

@@ -967,6 +967,64 @@ int gfv_sweep_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
                       int32_t* state, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Time march (gfv/march.py; solve_with_grad_GPU.py:133-209 with the --residual_tolerance / --max_inner_steps of
+ * utils/get_param.py:54-55): advance in time only after the inner iterations of a time level have converged, decided on the
+ * device.  ONE launch per training step, on the main stream, behind the backward and in front of the optimiser's launches.
+ * Beside what gfv_rollout_advance takes (uvp_node, x_backup, x, N, the chunk tables, B, losses, partial_ws):
+ *   hyper      the 8 floats of gfv_adam_step_dev; [5], [6], [7] = w_cont, w_mom, w_press are read
+ *   march      16 32-bit words of the caller's, zeroed once, then the host-written words set:
+ *     [0] max_inner (int32, host)    inner iterations per level at most
+ *     [1] min_inner (int32, host)    ... and at least
+ *     [2] inner     (int32)          inner iterations taken in the open level
+ *     [3] apply     (int32)          1 if this step is a step, 0 if it is held - at the position the Adam, guard and log launches
+ *                                    read as accum[3] (gfv_adam_step_accum_dev, gfv_grad_guard_accum_dev, gfv_train_log_append)
+ *     [4] tol       (float, host)    relative tolerance on r / r0; negative: never fires
+ *     [5] abs_tol   (float, host)    absolute tolerance on r; negative: never fires
+ *     [6] level     (int32)          levels completed
+ *     [7]           (int32)          arrival counter, zero between launches
+ *     [8] target    (int32, host)    levels to complete
+ *     [9] done      (int32)          1 once level >= target (or the history is full)
+ *     [10] seen     (int32)          launches that found done clear
+ *     [11] held     (int32)          launches that found done set
+ *     [12] keep     (int32, host)    snapshots kept, 0 .. the argument `keep`
+ *     [13..15]                       zero
+ *   r0         [B] float: the residual of each graph at the first inner iteration of the open level
+ *   history    [max_levels, GFV_MARCH_HEAD + GFV_MARCH_GRAPH * B] 32-bit words, one row per completed level:
+ *                head {level, inner iterations taken, flags GFV_MARCH_CONVERGED | GFV_MARCH_CAPPED, seen, 0, 0, 0, 0} (int32),
+ *                then per graph 8 floats: the four loss terms (bit copies), r0, r, || uvp_node - uvp_prev ||_2, || uvp_node ||_2
+ *   max_inner, min_inner   the values the host has written to march[0] and [1]: the entry point cannot read device memory, so it
+ *              checks these; the kernel reads the record's (a recorded launch follows a later host write) and, should they be out
+ *              of range there, uses max(max_inner, 1) and min_inner clamped to [1, max_inner]
+ *   snap, keep an optional ring [keep, N, 3] float of the last levels' fields (keep == 0: snap may be NULL); the kernel uses
+ *              min(march[12], keep) rows of it
+ *   mirror_dev optional: the device address of 3 pinned, device-mapped int32 (gfv_sweep_mirror_create) that receive {seen, level,
+ *              done} by plain stores - a hint the host reads without a synchronisation
+ * The rule, with the record AS THE LAUNCH FINDS IT (every workgroup reads it, r0 and losses before anything is written; the
+ * workgroup that arrives last writes it - the discipline of gfv_grad_accum_dev):
+ *   done set:     apply = 0; held += 1.  Nothing else changes.
+ *   done not set: apply = 1; seen += 1; per graph r = w_press * press + w_cont * cont + w_mom * mom_x + w_mom * mom_y in fp32, the
+ *                 statement that forms the argument of the logarithm in gfv_train_loss_dev (one shared inline function);
+ *                 inner == 0: r0 = r;  conv = (tol >= 0 && r <= tol * r0) || (abs_tol >= 0 && r <= abs_tol) - the product one fp32
+ *                 rounding, a NaN compares false;  k = inner + 1;  latch = (every graph conv && k >= min_inner) || k >= max_inner
+ *     no latch:   inner = k.  No row of x_backup, x or uvp_node is read or written.
+ *     latch:      x_backup[:, 0:3] = uvp_node; x = x_backup; snap[level % keep] = uvp_node; history row `level` (norms in the
+ *                 summation order of gfv_rollout_advance: double partial sums per chunk, folded per graph by the workgroup that
+ *                 arrives last, one rounding to fp32; no floating-point atomics); inner = 0; level += 1; done = level >= target.
+ *                 With level >= max_levels no row is written and done is set.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer (snap: only with keep > 0; mirror_dev: never), N, n_chunks, B or max_levels
+ * < 1, keep < 0, max_inner < 1, min_inner outside [1, max_inner] or an x_backup / x that is not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_MARCH_RECORD 16
+#define GFV_MARCH_HEAD 8
+#define GFV_MARCH_GRAPH 8
+#define GFV_MARCH_CONVERGED 1u
+#define GFV_MARCH_CAPPED 2u
+int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t N, const int32_t* chunk_beg,
+                      const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* losses,
+                      double* partial_ws, const float* hyper, int32_t* march, float* r0, void* history, int32_t max_levels,
+                      int32_t max_inner, int32_t min_inner, float* snap, int32_t keep, int32_t* mirror_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Evaluation over a device pool (gfv/evaluate.py; the training objective of pre_train_Adam.py:177-184 and field errors on
  * entries that are not trained on).  ONE launch behind the forward-only step of a batch turns its outputs into a record of
  * GFV_EVAL_RECORD floats per graph and writes it to row entry[b] of table [n_entries, GFV_EVAL_RECORD]:
