@@ -33,6 +33,11 @@ and decodes the history.  A later `run()` raises the target and clears `done`, a
 Who owns what a recorded list points at: DESIGN.md 5l.  Particular to this object, created in the constructor and held for its
 lifetime, never reallocated: the march record, r0, the history, the snapshot ring, the reduction workspace, the pinned mirror.
 One batch per object: `set_batch()` is refused.  The march state is not part of `state_dict()`.
+
+`schedule=` (gfv/schedule.py): the reference steps its scheduler once per time level (solve_with_grad_GPU.py:197).
+With a schedule attached every step issues one more launch in front of the march launch (`gfv_lr_schedule`, mode FOLLOW): the
+schedule's epoch becomes the level count, capped at the last level that runs, and that level's rate is written where Adam reads it.
+The step that ends a level runs at that level's rate; held steps change neither the rate nor the schedule's record.
 """
 from __future__ import annotations
 
@@ -46,6 +51,7 @@ import torch
 
 from . import lib as L
 from .optstep import optimizer_launches
+from .schedule import Plateau
 from .trainer import TrainStep
 
 # words of the march record (include/gfv.h gfv_march_advance)
@@ -91,6 +97,9 @@ def check_step_args(use_graph, kw):
         raise ValueError("MarchStep: data parallelism is not supported (the ranks would have to agree on every level's end)")
     if not kw.get("want_outputs", True):
         raise ValueError("MarchStep: want_outputs=False leaves no prediction to advance to")
+    if isinstance(kw.get("schedule"), Plateau):
+        raise ValueError("MarchStep: a Plateau schedule is not supported (the per-level launch follows the level count: it has no "
+                         "metric to observe)")
 
 
 def decode_history(words, B):
@@ -151,6 +160,10 @@ class MarchStep(TrainStep):
     def _put(self, word, ints):
         """Host words into the record, in stream order (the other words are the device's and stay)."""
         self._march[word:word + len(ints)].copy_(torch.tensor(ints, dtype=torch.int32))
+        if word == TARGET and self.schedule is not None:
+            # the schedule follows the level count up to the last level that runs: a step issued past the target (held) finds
+            # level == target and must leave the rate and the schedule's record as they are
+            self.schedule.set_follow_cap(int(ints[0]) - 1)
 
     def _write_control(self):
         self._put(MAX_INNER, [self._max_inner, self._min_inner])
@@ -189,6 +202,10 @@ class MarchStep(TrainStep):
     # ---- the step ------------------------------------------------------------------------------------------------------------
     def _after_backward(self):
         pl = self.plan
+        if self.schedule is not None:
+            # one scheduler step per time level (solve_with_grad_GPU.py:197), in front of the march launch: the level word shows
+            # every latch up to the previous step, so the step that ends a level still runs at that level's rate
+            self.schedule.follow(self._march.data_ptr() + 4 * LEVEL)
         L.check(L.load().gfv_march_advance(
             self.uvp_node.data_ptr(), self.x_backup.data_ptr(), self.x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(),
             pl.chunk_end.data_ptr(), pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, self.losses.data_ptr(), self._partial.data_ptr(),

@@ -46,6 +46,7 @@ from .accum import check_accum_steps
 from .ema import check_ema
 from .groups import check_groups
 from .guard import check_policy
+from .schedule import check_schedule
 from .static_forward import prep_scratch
 from .trainer import TrainStep
 from .trainlog import make_log
@@ -60,13 +61,14 @@ class PoolTrainStep(TrainStep):
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
         check_accum_steps(accum_steps, bool(distributed))
         check_ema(ema_decay, ema_warmup)
         check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
+        check_schedule(schedule)
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
@@ -76,7 +78,8 @@ class PoolTrainStep(TrainStep):
                          want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
                          skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
                          ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
-                         decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, log=log)
+                         decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, log=log,
+                         schedule=schedule)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = listcache.ListCache(self.max_list_bytes)     # key -> Entry with engine_sig, early, scratch

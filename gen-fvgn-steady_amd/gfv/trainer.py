@@ -24,6 +24,7 @@ from .groups import ParamGroups, check_groups, check_weight_decay
 from .guard import GradGuard, check_policy
 from .optstep import optimizer_launches
 from .plan import _live_key, _refresh_live, get_plan
+from .schedule import check_schedule
 from .trainlog import make_log
 
 
@@ -35,7 +36,7 @@ class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None):
         # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
         # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
         dist_on = (world_size > 1) if distributed is None else bool(distributed)
@@ -43,6 +44,8 @@ class TrainStep:
         accum_steps = check_accum_steps(accum_steps, dist_on)
         ema_decay = check_ema(ema_decay, ema_warmup)
         spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
+        check_schedule(schedule)
+        self.schedule = None
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -106,6 +109,12 @@ class TrainStep:
         spec.skip = set(self.G.skip)
         spec.check_some_live([g["frozen"] for g in spec.groups])
         self._groups_changed(frozen_changed=bool(spec.frozen_names()))
+        # learning-rate schedule (gfv/schedule.py): None - no launch, no allocation, `ts.lr = v` as it was.  Attached,
+        # it owns hyper[0] and the lr word of every group row: one EVAL launch here, `ts.schedule.tick()` per epoch
+        if schedule is not None:
+            self.schedule = schedule
+            schedule._attach(self)
+            self._lr = schedule.base_lr                             # (ts.lr reads back the base rate)
         # training log (gfv/trainlog.py): None with log=None - no launch, no allocation.  An int capacity, a
         # TrainLog or a dict of its arguments; its two launches follow every step eagerly (_log_step), outside lists and graphs
         self.log = make_log(log, self.plan.B)
@@ -153,12 +162,23 @@ class TrainStep:
         vals = (self._lr, self._betas[0], self._betas[1], self._eps, 1.0 / self.world_size, *self._lw)
         if vals != self._hyper_host:
             betas_moved = self._hyper_host is None or vals[1:3] != self._hyper_host[1:3]
-            self.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+            if self.schedule is None:
+                self.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
+            else:
+                self.hyper[1:].copy_(torch.tensor(vals[1:], dtype=torch.float32))   # (word 0 is the schedule's)
             self._hyper_host = vals
             if betas_moved:
                 self._init_adam_state()
         if self._pg is not None:
             self._pg.sync(self._gs.values(self._lr), self._gs.decoupled)   # (every group's rate is lr * lr_scale)
+            self._sched_eval()
+
+    def _sched_eval(self):
+        """Behind every host write of the group table: the schedule's scales follow the groups and one EVAL launch puts the
+        scheduled rate back into the rows (in stream order: no step runs in between)."""
+        if self.schedule is not None:
+            self.schedule._sync_scales()
+            self.schedule.eval()
 
     def _init_adam_state(self, steps_done=None):
         """The device-side bias corrections of the next step, from the step count (a new object, a loaded checkpoint, new betas)."""
@@ -176,6 +196,8 @@ class TrainStep:
 
     @lr.setter
     def lr(self, v):
+        if self.schedule is not None:
+            raise RuntimeError("the attached schedule owns the learning rate (ts.schedule.tick(); ts.lr reads the base rate)")
         self._lr = float(v)
         self._sync_hyper()
 
@@ -237,6 +259,7 @@ class TrainStep:
             self._stateful = self._live_names()
             self._drop_recorded()
         self._pg.sync(gs.values(self._lr), gs.decoupled)
+        self._sched_eval()
         if frozen_changed:
             frozen = gs.frozen_names()
             self._stateful |= self._live_names()
@@ -435,6 +458,8 @@ class TrainStep:
             avg = self.ema_parameters()
             sd["gfv_ema"] = {"decay": self._ema.decay, "warmup": self._ema.warmup, "updates": self._ema.stats()["updates"],
                              "params": [avg[n] for n in names]}
+        if self.schedule is not None:
+            sd["gfv_schedule"] = self.schedule.state_dict()       # (epoch, rate, plateau state: one synchronisation)
         return sd
 
     def load_state_dict(self, sd):
@@ -448,6 +473,9 @@ class TrainStep:
             raise ValueError("per-parameter step counts differ: not a state this fused Adam can resume")
         step = steps.pop() if steps else None
         plan = self._plan_groups(sd, names)
+        sched = sd.get("gfv_schedule") if self.schedule is not None else None
+        if sched is not None and sched.get("kind") != type(self.schedule).__name__:
+            raise ValueError(f"the state of a {sched.get('kind')} schedule does not load into a {type(self.schedule).__name__}")
         self.flat_m.zero_()
         self.flat_v.zero_()
         for i, st in sd["state"].items():
@@ -487,6 +515,10 @@ class TrainStep:
                     self.G.view_of(self._ema.e, n).copy_(t.reshape(self.G.shape[n]))
                 self._ema_warmup = bool(avg["warmup"])
                 self._ema.set(check_ema(avg["decay"]), self._ema_warmup, int(avg["updates"]))
+        if self.schedule is not None:
+            self._lr = self.schedule.base_lr
+            if sched is not None:
+                self.schedule.load_state_dict(sched)
 
     def _plan_groups(self, sd, names):
         """What a state_dict says about the groups, checked and nothing changed: None for a dict without groups (one group over

@@ -1025,6 +1025,76 @@ int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
                       int32_t max_inner, int32_t min_inner, float* snap, int32_t keep, int32_t* mirror_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
+ * at pre_train_Adam.py:203 and solve_with_grad_GPU.py:197, and torch.optim.lr_scheduler.ReduceLROnPlateau).  ONE launch of one
+ * wave recomputes the rate from a device record and writes it where the Adam launches read it:
+ *   hyper[0] = (float)lr                        (the 8 floats of gfv_adam_step_dev; no other word is touched)
+ *   group row k, word 0 = (float)(lr * scales[k])   for k < n_groups: `group_table` is the table of gfv_adam_step_groups_dev
+ *                                               ((GFV_MAX_PARAM_GROUPS + 2) * 8 words, row 0 its header; group k is row 1 + k),
+ *                                               the product formed in double from the unrounded rate.  NULL: no groups.
+ * rec: GFV_SCHED_RECORD doubles (8-byte aligned) of the caller's, addressed as 32-bit words w[] and as doubles d[]:
+ *     w[0]  kind            (host)   GFV_SCHED_STEPEXP .. GFV_SCHED_PLATEAU
+ *     w[1]  epoch
+ *     w[2]  n_milestones    (host)   GRADUAL: 0 .. GFV_SCHED_MAX_MILESTONES
+ *     w[3]  num_bad                  PLATEAU: epochs without improvement
+ *     w[4]  cooldown_left            PLATEAU
+ *     w[5]  patience        (host)   PLATEAU
+ *     w[6]  cooldown        (host)   PLATEAU
+ *     w[7]  warmup_epochs   (host)   PLATEAU: 0 = no warm-up
+ *     w[8]  steplr_milestone (host)  STEPEXP
+ *     w[9]  explr_milestone (host)   STEPEXP
+ *     w[10] total_epoch     (host)   STEPEXP, GRADUAL
+ *     w[11] follow_cap      (host)   FOLLOW: the largest epoch it sets; negative: none
+ *     w[12..15]                      zero
+ *     d[8]  lr                       the current unrounded rate
+ *     d[9]  base_lr         (host)
+ *     d[10] min_lr          (host)
+ *     d[11] gamma           (host)   STEPEXP: steplr_gamma; EXP, GRADUAL: gamma
+ *     d[12] expgamma        (host)   STEPEXP: explr_gamma; GRADUAL: expgamma
+ *     d[13] decay_steps     (host)   STEPEXP: total_epoch - explr_milestone
+ *     d[14] startlr         (host)   STEPEXP
+ *     d[15] best                     PLATEAU: +inf at the start
+ *     d[16] factor, d[17] threshold, d[18] eps, d[19] multiplier   (host)   PLATEAU
+ *     w[40..47] milestones  (host)   GRADUAL, int32
+ *   Words marked (host) are written by the host only; the others by the kernel (and by the host when a state is loaded).
+ * mode, with the record AS THE LAUNCH FINDS IT:
+ *   GFV_SCHED_EVAL    epoch unchanged; the rate is recomputed and written out.  Idempotent: for after the host has rewritten hyper
+ *                     or the group table for another reason.
+ *   GFV_SCHED_TICK    epoch += 1, then as EVAL - the host's lr_scheduler.step().  PLATEAU past its warm-up observes *metric first.
+ *   GFV_SCHED_FOLLOW  c = *counter (a 32-bit word, e.g. word [6] `level` of gfv_march_advance's record), c = min(c, follow_cap)
+ *                     when follow_cap >= 0; epoch = c if it differs; then as EVAL.  PLATEAU: as EVAL (there is no metric).
+ * The rate of epoch e, every operation one IEEE double operation in the order written (pow is the device library's):
+ *   STEPEXP   e < steplr_milestone: startlr;  e < explr_milestone: startlr * gamma;
+ *             else min_lr + max(base_lr * gamma - min_lr, 0) * pow(expgamma, (e - explr_milestone) / decay_steps)
+ *   EXP       min_lr + max(base_lr - min_lr, 0) * pow(gamma, e / decay_steps)
+ *   GRADUAL   hit = the number of milestones <= min(e, total_epoch);  s = base_lr * pow(gamma, hit);
+ *             e <= total_epoch: s;  else min_lr + max(s - min_lr, 0) * pow(expgamma, (e - total_epoch) / decay_steps)
+ *   TABLE     table[min(max(e, 0), table_len - 1)] - a device array of doubles; without a table the rate stays
+ *   PLATEAU   0 < e <= warmup_epochs: base_lr * (e / warmup_epochs) if multiplier == 1, else
+ *             base_lr * ((multiplier - 1) * e / warmup_epochs + 1); nothing is observed.  Otherwise the rate stays, and a TICK
+ *             observes a = (double)*metric as ReduceLROnPlateau(mode "min", threshold_mode "rel") does:
+ *             a < best * (1 - threshold) ? (best = a, num_bad = 0) : num_bad += 1  (a NaN compares false: a bad epoch);
+ *             cooldown_left > 0: cooldown_left -= 1, num_bad = 0;
+ *             num_bad > patience: n = max(lr * factor, min_lr); lr - n > eps: lr = n;  cooldown_left = cooldown; num_bad = 0.
+ *             A TICK with metric NULL observes nothing.
+ * GFV_ERR_ARG (nothing launched) on rec or hyper NULL, a rec that is not 8-byte aligned, an unknown mode, FOLLOW without counter,
+ * n_groups outside [0, GFV_MAX_PARAM_GROUPS], group_table with n_groups > 0 and scales NULL, table_len < 0 or table_len > 0 with
+ * table NULL.  The kind is the record's: the entry point cannot read it.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_SCHED_RECORD 32
+#define GFV_SCHED_MAX_MILESTONES 8
+#define GFV_SCHED_EVAL 0
+#define GFV_SCHED_TICK 1
+#define GFV_SCHED_FOLLOW 2
+#define GFV_SCHED_STEPEXP 1
+#define GFV_SCHED_EXP 2
+#define GFV_SCHED_GRADUAL 3
+#define GFV_SCHED_TABLE 4
+#define GFV_SCHED_PLATEAU 5
+int gfv_lr_schedule(double* rec, int32_t mode, float* hyper, float* group_table, const double* scales, int32_t n_groups,
+                    const double* table, int32_t table_len, const float* metric, const int32_t* counter, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Evaluation over a device pool (gfv/evaluate.py; the training objective of pre_train_Adam.py:177-184 and field errors on
  * entries that are not trained on).  ONE launch behind the forward-only step of a batch turns its outputs into a record of
  * GFV_EVAL_RECORD floats per graph and writes it to row entry[b] of table [n_entries, GFV_EVAL_RECORD]:
