@@ -16,6 +16,10 @@ batch of a `BatchArena` with one launch behind it (`gfv_eval_collect`, csrc/eval
 
 The pool is NOT written: no payback, no advance - every entry's `x` is bit for bit what it was.
 
+The objective is formed with this object's own fixed `loss_weights` (the model's constants unless given), also when the training
+step carries a balancer (`balance=`, gfv/balance.py) that moves ITS weights from step to step: a held-out objective stays comparable
+across epochs.  Pass `loss_weights=ts.loss_weights` to evaluate under the training step's base weights.
+
 Per batch: `arena.load(batch)`; the targets of its entries copied into the staging buffer at the host-known node offsets; the
 body - `Sweep._body` without the advance: `StaticForward.forward` and nothing behind it - eager, recorded or replayed; then
 `gfv_eval_collect`, which writes a 16-float record per graph into row `entry` of a device table `[n_entries, 16]` (the layout is in

@@ -114,6 +114,9 @@ MARCH_RECORD, MARCH_HEAD, MARCH_GRAPH, MARCH_CONVERGED, MARCH_CAPPED = 16, 8, 8,
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
 SCHED_STEPEXP, SCHED_EXP, SCHED_GRADUAL, SCHED_TABLE, SCHED_PLATEAU = 1, 2, 3, 4, 5
+# GFV_BALANCE_* of include/gfv.h: doubles of a balance record, partial sums of the statistic, the kinds of gfv_loss_balance
+BALANCE_RECORD, BALANCE_LANES = 32, 64
+BALANCE_INVERSE, BALANCE_PROGRESS = 1, 2
 POOL_COPY, POOL_ADD, POOL_ROWPTR, POOL_FILL = 0, 1, 2, 3
 
 
@@ -286,6 +289,7 @@ _SIGNATURES = {
                                                                      C.c_void_p, C.c_void_p]),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_eval_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

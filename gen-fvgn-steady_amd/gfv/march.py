@@ -97,6 +97,9 @@ def check_step_args(use_graph, kw):
         raise ValueError("MarchStep: data parallelism is not supported (the ranks would have to agree on every level's end)")
     if not kw.get("want_outputs", True):
         raise ValueError("MarchStep: want_outputs=False leaves no prediction to advance to")
+    if kw.get("balance") is not None:
+        raise ValueError("MarchStep: balance= is not supported (the convergence test compares r with r0 under ONE set of weights; "
+                         "a balancer would move them within a level)")
     if isinstance(kw.get("schedule"), Plateau):
         raise ValueError("MarchStep: a Plateau schedule is not supported (the per-level launch follows the level count: it has no "
                          "metric to observe)")

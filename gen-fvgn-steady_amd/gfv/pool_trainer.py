@@ -43,6 +43,7 @@ from . import cmdlist
 from . import lib as L
 from . import listcache
 from .accum import check_accum_steps
+from .balance import check_balance
 from .ema import check_ema
 from .groups import check_groups
 from .guard import check_policy
@@ -61,7 +62,7 @@ class PoolTrainStep(TrainStep):
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
@@ -69,6 +70,7 @@ class PoolTrainStep(TrainStep):
         check_ema(ema_decay, ema_warmup)
         check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         check_schedule(schedule)
+        check_balance(balance, bool(distributed), 1, "PoolTrainStep")
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
@@ -79,7 +81,7 @@ class PoolTrainStep(TrainStep):
                          skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
                          ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
                          decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, log=log,
-                         schedule=schedule)
+                         schedule=schedule, balance=balance)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = listcache.ListCache(self.max_list_bytes)     # key -> Entry with engine_sig, early, scratch
@@ -190,6 +192,7 @@ class PoolTrainStep(TrainStep):
         if self._accum is not None:
             self._accum.note_step()
         self._log_step(idx, self.pool.n)     # (eager, behind Adam, outside the list: the row carries this step's entries)
+        self._balance_step()                 # (eager, outside the list too: losses differs per list, B per batch)
         if payback or advance:
             if self.uvp_node is None:
                 raise RuntimeError("payback needs the prediction of the step (want_outputs=True)")

@@ -17,6 +17,7 @@ import torch
 from . import cmdlist
 from . import lib as L
 from .accum import GradAccum, check_accum_steps
+from .balance import check_balance
 from .ema import WeightEMA, check_ema
 from .engine import GradStore
 from .functions import unused_param_names
@@ -36,7 +37,7 @@ class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None):
         # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
         # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
         dist_on = (world_size > 1) if distributed is None else bool(distributed)
@@ -45,7 +46,9 @@ class TrainStep:
         ema_decay = check_ema(ema_decay, ema_warmup)
         spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         check_schedule(schedule)
+        check_balance(balance, dist_on, world_size, type(self).__name__)
         self.schedule = None
+        self.balance = None
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -115,6 +118,11 @@ class TrainStep:
             self.schedule = schedule
             schedule._attach(self)
             self._lr = schedule.base_lr                             # (ts.lr reads back the base rate)
+        # loss balancing (gfv/balance.py): None - no launch, no allocation, `ts.loss_weights = v` as it was.  Attached,
+        # it owns hyper[5:8]: the constructor's loss_weights are its base weights, one launch follows every step (_balance_step)
+        if balance is not None:
+            self.balance = balance
+            balance._attach(self)
         # training log (gfv/trainlog.py): None with log=None - no launch, no allocation.  An int capacity, a
         # TrainLog or a dict of its arguments; its two launches follow every step eagerly (_log_step), outside lists and graphs
         self.log = make_log(log, self.plan.B)
@@ -162,10 +170,12 @@ class TrainStep:
         vals = (self._lr, self._betas[0], self._betas[1], self._eps, 1.0 / self.world_size, *self._lw)
         if vals != self._hyper_host:
             betas_moved = self._hyper_host is None or vals[1:3] != self._hyper_host[1:3]
-            if self.schedule is None:
+            if self.schedule is None and self.balance is None:
                 self.hyper.copy_(torch.tensor(vals, dtype=torch.float32))
             else:
-                self.hyper[1:].copy_(torch.tensor(vals[1:], dtype=torch.float32))   # (word 0 is the schedule's)
+                # (word 0 is the schedule's, words 5 .. 7 are the balancer's)
+                lo, hi = (0 if self.schedule is None else 1), (8 if self.balance is None else 5)
+                self.hyper[lo:hi].copy_(torch.tensor(vals[lo:hi], dtype=torch.float32))
             self._hyper_host = vals
             if betas_moved:
                 self._init_adam_state()
@@ -213,6 +223,9 @@ class TrainStep:
 
     @loss_weights.setter
     def loss_weights(self, v):
+        if self.balance is not None:
+            raise RuntimeError("the attached balancer owns the loss weights (ts.balance.set_base(weights) gives it new base "
+                               "weights; ts.loss_weights reads the base weights)")
         self._lw = tuple(float(x) for x in v)
         self._sync_hyper()
 
@@ -460,6 +473,8 @@ class TrainStep:
                              "params": [avg[n] for n in names]}
         if self.schedule is not None:
             sd["gfv_schedule"] = self.schedule.state_dict()       # (epoch, rate, plateau state: one synchronisation)
+        if self.balance is not None:
+            sd["gfv_balance"] = self.balance.state_dict()         # (the record's device-written words: one synchronisation)
         return sd
 
     def load_state_dict(self, sd):
@@ -476,6 +491,9 @@ class TrainStep:
         sched = sd.get("gfv_schedule") if self.schedule is not None else None
         if sched is not None and sched.get("kind") != type(self.schedule).__name__:
             raise ValueError(f"the state of a {sched.get('kind')} schedule does not load into a {type(self.schedule).__name__}")
+        bal = sd.get("gfv_balance") if self.balance is not None else None
+        if bal is not None and bal.get("kind") != type(self.balance).__name__:
+            raise ValueError(f"the state of a {bal.get('kind')} balancer does not load into a {type(self.balance).__name__}")
         self.flat_m.zero_()
         self.flat_v.zero_()
         for i, st in sd["state"].items():
@@ -519,6 +537,13 @@ class TrainStep:
             self._lr = self.schedule.base_lr
             if sched is not None:
                 self.schedule.load_state_dict(sched)
+        if self.balance is not None:
+            if bal is not None:
+                self.balance.load_state_dict(bal)                 # (the record and hyper[5:8]; ts.loss_weights = its base weights)
+            else:
+                # a dict without a balancer's state: a new record over the loaded base weights
+                self.balance.set_base(self._lw)
+                self.balance.reset()
 
     def _plan_groups(self, sd, names):
         """What a state_dict says about the groups, checked and nothing changed: None for a dict without groups (one group over
@@ -698,6 +723,16 @@ class TrainStep:
                         guard=self._guard.guard if self._guard.active else None,
                         accum=None if self._accum is None else self._accum.rec, entries=entries, n_entries=n_entries)
 
+    def _balance_step(self):
+        """The balancer's launch (gfv/balance.py), eagerly on the current stream behind the optimiser launches of the step and
+        behind the log's (a row shows the weights its step used) - whichever way the step was issued: `_log_step`'s rule.  It
+        observes this step's terms and may write hyper[5:8] for the NEXT step.  Under accumulation the record's apply word is its
+        hold word: every micro-step is observed, the weights move only behind an applied step.  A step the guard skipped is
+        observed too (an observation is about losses, not gradients); non-finite terms reject themselves."""
+        if self.balance is None:
+            return
+        self.balance.observe(self.losses, self.plan.B, self.hyper, None if self._accum is None else self._accum.rec_i[3:4])
+
     def _check_aliasing(self):
         """The module's parameters must still be the views of the flat buffer this object made them (a `model.to()`, a
         `load_state_dict(assign=True)` or a second TrainStep on the same model re-points them): captured steps hold raw
@@ -800,6 +835,7 @@ class TrainStep:
         if self._accum is not None:
             self._accum.note_step()
         self._log_step()
+        self._balance_step()
         return self.loss
 
     # state snapshot so the capture warm-up does not advance training ---------------------------------------

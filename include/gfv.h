@@ -1095,6 +1095,67 @@ int gfv_lr_schedule(double* rec, int32_t mode, float* hyper, float* group_table,
                     const double* table, int32_t table_len, const float* metric, const int32_t* counter, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Loss balancing: the three residual weights adapted on the device (gfv/balance.py).  The objective is
+ * mean_b log(w_press * press_b + w_cont * cont_b + w_mom * (mom_x_b + mom_y_b)); the reference ships the weights as constants
+ * (utils/get_param.py:59-61).  Here they live in hyper[5..7] (w_cont, w_mom, w_press: what the loss launch, its gradient and the
+ * march read), and ONE launch of one wave per training step, BEHIND that step's optimiser launches, observes the step's terms and
+ * may write new weights there for the NEXT step.  Classes k = 0, 1, 2: cont, mom, press - the order of hyper[5], hyper[6], hyper[7].
+ *
+ * losses: [B, 4] fp32 (cont, mom_x, mom_y, press) of the step, B >= 1.  The statistic of a launch, all in double:
+ *   t_0(b) = (double)losses[b,0];  t_1(b) = (double)losses[b,1] + (double)losses[b,2];  t_2(b) = (double)losses[b,3]
+ *   s_k = (sum_b t_k(b)) / (double)B, the sum in this fixed order, whatever the launch geometry: GFV_BALANCE_LANES = 64 partial
+ *   sums, p_j = t_k(j) + t_k(j + 64) + t_k(j + 128) + ... added from the left starting at 0.0 (a j without a graph: 0.0); then
+ *   for h = 32, 16, 8, 4, 2, 1:  p_j = p_j + p_(j+h) for j < h;  the sum is p_0.  No floating-point atomics.
+ * rec: GFV_BALANCE_RECORD doubles (8-byte aligned) of the caller's, addressed as 32-bit words w[] and as doubles d[]:
+ *     w[0]  kind            (host)   GFV_BALANCE_INVERSE or GFV_BALANCE_PROGRESS
+ *     w[1]  warmup          (host)   observations before the first publish, >= 0
+ *     w[2]  every           (host)   publish behind every `every`-th applied step, >= 1 (below 1: taken as 1)
+ *     w[3]  n                        observations accepted
+ *     w[4]  n_applied                accepted observations behind an applied step
+ *     w[5]  n_updates                publishes
+ *     w[6]  n_skipped                observations rejected
+ *     w[7]                           zero
+ *     d[4]  decay           (host)   of the moving average, in [0, 1)
+ *     d[5]  floor           (host)   > 0
+ *     d[6]  alpha           (host)   PROGRESS: in [0, 1)
+ *     d[7]  tau             (host)   PROGRESS: > 0
+ *     d[8..10]  g           (host)   INVERSE: the shares, each > 0
+ *     d[11..13] w0          (host)   the base weights
+ *     d[14] power                    decay^n, 1 at the start
+ *     d[15..17] m                    the moving average, 0 at the start
+ *     d[18..20] s                    the last accepted statistic
+ *     d[21..23] s_ref                the reference statistic
+ *     d[24..26] lam                  the multipliers, 1 at the start
+ *     d[27..29] w                    the current weights, w0 at the start
+ *     d[30..31]                      zero
+ *   Words marked (host) are written by the host only; the others by the kernel (and by the host when a state is loaded).
+ * The rule, with the record AS THE LAUNCH FINDS IT; every operation is one IEEE double operation in the order written (the unit is
+ * built without contraction; exp is the device library's):
+ *   1. s as above.  If any s_k is NaN, infinite or negative: n_skipped += 1, nothing else changes, hyper is not written.
+ *   2. n += 1;  m_k = decay * m_k + (1 - decay) * s_k;  power = power * decay;  mh_k = m_k / (1 - power)  (decay == 0: mh = s);
+ *      at n == 1: s_ref = mh.
+ *   3. applied = hold == NULL or *hold != 0.  hold is word [3] `apply` of the accumulation record of gfv_grad_accum_dev, the word
+ *      the guard, Adam and log launches read.  If applied: n_applied += 1.
+ *   4. A publish happens if applied and n > warmup and n_applied % every == 0:
+ *      INVERSE   R0 = (w0_0 * mh_0 + w0_1 * mh_1) + w0_2 * mh_2;  G = (g_0 + g_1) + g_2;
+ *                w_k = ((g_k / G) * R0) / max(mh_k, floor).
+ *                Every class then contributes its share g_k / G of the residual R0 that the base weights would give.
+ *      PROGRESS  rho_k = mh_k / max(s_ref_k, floor);  z_k = rho_k / tau;  zm = max(z_0, z_1, z_2);  e_k = exp(z_k - zm);
+ *                E = (e_0 + e_1) + e_2;  lh_k = 3 * (e_k / E);  lam_k = alpha * lam_k + (1 - alpha) * lh_k;  w_k = w0_k * lam_k;
+ *                s_ref = mh.  (ReLoBRaLo of Bischof and Kraus without its random look-back: a term that falls more slowly than
+ *                the others gains weight; the sum of lam stays 3.)
+ *      then hyper[5 + k] = (float)w_k, the record's w = w, n_updates += 1.  No other word of hyper is touched.
+ * One wave: every lane loads the record, the hold word and its share of losses; all loads stand in front of all stores in program
+ * order; lane 0 writes the record and hyper with ordinary vector stores.  No atomics, no arrival counter.
+ * GFV_ERR_ARG (nothing launched) on losses, rec or hyper NULL, B < 1, a rec that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_BALANCE_RECORD 32
+#define GFV_BALANCE_LANES 64
+#define GFV_BALANCE_INVERSE 1
+#define GFV_BALANCE_PROGRESS 2
+int gfv_loss_balance(const float* losses, int32_t B, double* rec, float* hyper, const int32_t* hold_or_null, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Evaluation over a device pool (gfv/evaluate.py; the training objective of pre_train_Adam.py:177-184 and field errors on
  * entries that are not trained on).  ONE launch behind the forward-only step of a batch turns its outputs into a record of
  * GFV_EVAL_RECORD floats per graph and writes it to row entry[b] of table [n_entries, GFV_EVAL_RECORD]:
