@@ -1486,13 +1486,17 @@ class Engine:
         losses, uvp_node, uvp_cell, sv_fvm = self.fvm_fwd(dec, uv_old, pl, want_outputs, train_loss=train_loss, keep=keep)
         return losses, uvp_node, uvp_cell, ea15, (dict(sim=sv_sim, fvm=sv_fvm) if keep else None)
 
-    def backward(self, P, ctx, gloss, grads, pl):
-        """gloss [B,4] = dL/d(cont, mom_x, mom_y, press); fills `grads` (name -> preallocated tensor)."""
+    def backward(self, P, ctx, gloss, grads, pl, g_dec_hook=None):
+        """gloss [B,4] = dL/d(cont, mom_x, mom_y, press); fills `grads` (name -> preallocated tensor).
+        g_dec_hook(g_dec): main-stream launches of the caller that add to the decoder-output gradient [N,3] between the
+        finite-volume adjoint and the decoder's backward (gfv/observe.py); None: nothing is issued there."""
         with self.fork():   # transposed copies + their images: beside the finite-volume adjoint
             self.prepare_transposes(P)
             prev = self._wi_enter("bwd", P)
         try:
             g_dec = self.fvm_bwd(ctx["fvm"], gloss, pl)
+            if g_dec_hook is not None:
+                g_dec_hook(g_dec)
             self.join()
             self.simulator_bwd(P, ctx["sim"], g_dec, grads, pl)
             self.join()

@@ -117,6 +117,7 @@ SCHED_STEPEXP, SCHED_EXP, SCHED_GRADUAL, SCHED_TABLE, SCHED_PLATEAU = 1, 2, 3, 4
 # GFV_BALANCE_* of include/gfv.h: doubles of a balance record, partial sums of the statistic, the kinds of gfv_loss_balance
 BALANCE_RECORD, BALANCE_LANES = 32, 64
 BALANCE_INVERSE, BALANCE_PROGRESS = 1, 2
+OBS_RECORD = 4   # GFV_OBS_RECORD of include/gfv.h: floats per graph of the record gfv_obs_fwd writes (obs, W, gobs, tot)
 POOL_COPY, POOL_ADD, POOL_ROWPTR, POOL_FILL = 0, 1, 2, 3
 
 
@@ -290,6 +291,10 @@ _SIGNATURES = {
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gfv_obs_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32]
+                    + [C.c_void_p] * 11),
+    "gfv_obs_bwd": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gfv_obs_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "gfv_eval_collect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                    C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),

@@ -100,6 +100,9 @@ def check_step_args(use_graph, kw):
     if kw.get("balance") is not None:
         raise ValueError("MarchStep: balance= is not supported (the convergence test compares r with r0 under ONE set of weights; "
                          "a balancer would move them within a level)")
+    if kw.get("observations") is not None:
+        raise ValueError("MarchStep: observations= is not supported (the convergence rule is on the PDE residual alone; a data "
+                         "term inside the objective would not be seen by it)")
     if isinstance(kw.get("schedule"), Plateau):
         raise ValueError("MarchStep: a Plateau schedule is not supported (the per-level launch follows the level count: it has no "
                          "metric to observe)")

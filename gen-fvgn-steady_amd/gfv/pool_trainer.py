@@ -22,6 +22,11 @@ mean gradient of all their graphs.  The key of a list is unchanged: the launches
 micro-step and read their phase from a device record, so the list of a signature is replayed in every phase.  With micro-batches
 of one or two meshes a pool of N sizes has N or N^2 ordered signatures instead of N^8, and every list is small.
 
+Observations (`observations=gfv.observe.PoolObservations(pool)`): measured fields per pool entry enter the objective
+as a data term.  One launch behind `arena.load` and in front of the replay gathers the batch's entries into the observations'
+staging buffers (eager in every mode, never recorded); the two launches of the term are part of the recorded body and read those
+buffers, so the key of a list is unchanged.
+
 Who owns what a recorded list points at: DESIGN.md 5l.  Particular to this object, for its lifetime: the flat parameter /
 gradient / moment buffers, `loss`, the per-B `gloss`, the Adam state.  The weight-image set is checked through
 `Engine.capture_signature()`.  The engine scratch of a training step - `_zero_e`, `_dw_ws`, `_dw_ws_main`, `_prep_ws`,
@@ -47,6 +52,7 @@ from .balance import check_balance
 from .ema import check_ema
 from .groups import check_groups
 from .guard import check_policy
+from .observe import PoolObservations, check_observe
 from .schedule import check_schedule
 from .static_forward import prep_scratch
 from .trainer import TrainStep
@@ -58,11 +64,12 @@ _FIXED = ("_zero_e", "_prep_ws", "_fvm_cnt")       # sized once for the arena's 
 
 class PoolTrainStep(TrainStep):
     WARM, EVICT_MAX = listcache.WARM, listcache.EVICT_MAX
+    _OBS_KIND = PoolObservations
 
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
@@ -71,6 +78,9 @@ class PoolTrainStep(TrainStep):
         check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         check_schedule(schedule)
         check_balance(balance, bool(distributed), 1, "PoolTrainStep")
+        check_observe(observations, balance, "PoolTrainStep", PoolObservations)
+        if observations is not None and observations.pool is not pool:
+            raise ValueError("PoolTrainStep: the PoolObservations were built on another pool than the one to train on")
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
         self.max_list_bytes = int(max_list_bytes)
@@ -81,7 +91,7 @@ class PoolTrainStep(TrainStep):
                          skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
                          ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
                          decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, log=log,
-                         schedule=schedule, balance=balance)
+                         schedule=schedule, balance=balance, observations=observations)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
         self._graphs = listcache.ListCache(self.max_list_bytes)     # key -> Entry with engine_sig, early, scratch
@@ -154,6 +164,10 @@ class PoolTrainStep(TrainStep):
         if gl is None:
             gl = self._gloss[plan.B] = torch.zeros((plan.B, 4), dtype=torch.float32, device=self.dev)
         self.gloss = gl
+        if self.observations is not None:
+            # the batch's measured values and weights into the observations' staging buffers (gfv/observe.py): eager, in front of
+            # the step in every launch mode - the recorded body reads the buffers, never the entries
+            self.observations.gather(idx, plan)
         acc = self.model.node_norm.should_accumulate()
         dist_on = self.dist_on
         key = (sig, acc, dist_on)

@@ -23,6 +23,7 @@ from .engine import GradStore
 from .functions import unused_param_names
 from .groups import ParamGroups, check_groups, check_weight_decay
 from .guard import GradGuard, check_policy
+from .observe import Observations, check_observe
 from .optstep import optimizer_launches
 from .plan import _live_key, _refresh_live, get_plan
 from .schedule import check_schedule
@@ -34,10 +35,12 @@ def _gather(src, index, out):
 
 
 class TrainStep:
+    _OBS_KIND = Observations          # what `observations=` takes (PoolTrainStep: PoolObservations)
+
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None):
         # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
         # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
         dist_on = (world_size > 1) if distributed is None else bool(distributed)
@@ -47,8 +50,10 @@ class TrainStep:
         spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
         check_schedule(schedule)
         check_balance(balance, dist_on, world_size, type(self).__name__)
+        check_observe(observations, balance, type(self).__name__, self._OBS_KIND)
         self.schedule = None
         self.balance = None
+        self.observations = None
         self.model = model
         self.graphs = graphs
         self.plan = get_plan(graphs)
@@ -123,6 +128,11 @@ class TrainStep:
         if balance is not None:
             self.balance = balance
             balance._attach(self)
+        # observation term (gfv/observe.py): None - no launch, no allocation, the step body as it was.  Attached, two
+        # launches join the step body (_body): the loss launch's `loss` / `gloss` are overwritten, the decoder gradient added to
+        if observations is not None:
+            observations._attach(self)
+            self.observations = observations
         # training log (gfv/trainlog.py): None with log=None - no launch, no allocation.  An int capacity, a
         # TrainLog or a dict of its arguments; its two launches follow every step eagerly (_log_step), outside lists and graphs
         self.log = make_log(log, self.plan.B)
@@ -609,6 +619,9 @@ class TrainStep:
         """Switch to another batch (dataset training: a new batch every step, pre_train_Adam.py:146-156).  Captured
         hipGraphs belong to the tensors of one batch and are dropped; with a gfv.pool.DevicePool the switch costs one
         small launch."""
+        if self.observations is not None:
+            raise ValueError("set_batch() with observations attached: they belong to the nodes of ONE batch (changing batches are "
+                             "PoolTrainStep's and gfv.observe.PoolObservations' job)")
         self.graphs = graphs
         self.plan = get_plan(graphs)
         self._live = _live_key(graphs)
@@ -632,7 +645,14 @@ class TrainStep:
                 self.P_run, self.model.node_norm.buffers_dict(), self.x, self.plan, norm_global=True, accumulate=accumulate,
                 want_outputs=self.want_outputs, want_edge_attr15=False, x_raw=self.x_backup,
                 train_loss=(self.hyper, self.loss, self.gloss))   # loss + its gradient behind the residual norms, same launch
-            self.engine.backward(self.P_run, ctx, self.gloss, self.G_run, self.plan)
+            obs, hook = self.observations, None
+            if obs is not None:
+                # the data term (gfv/observe.py): loss and gloss re-formed with it behind the forward, its own gradient added to
+                # the decoder-output gradient inside the backward
+                fv, pl = ctx["fvm"], self.plan
+                obs.fwd(fv["phi"], pl, losses, self.hyper, self.loss, self.gloss)
+                hook = lambda g_dec: obs.bwd(fv["dec"], fv["phi"], pl, g_dec)
+            self.engine.backward(self.P_run, ctx, self.gloss, self.G_run, self.plan, g_dec_hook=hook)
         if self.padded:
             cmdlist.call(_gather, self.G_run.flat, self._unpad_map, self.flat_g)
         self.losses, self.uvp_node, self.uvp_cell = losses, uvp_node, uvp_cell

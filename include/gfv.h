@@ -1156,6 +1156,50 @@ int gfv_lr_schedule(double* rec, int32_t mode, float* hyper, float* group_table,
 int gfv_loss_balance(const float* losses, int32_t B, double* rec, float* hyper, const int32_t* hold_or_null, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Observation term: measured fields beside the PDE residual (gfv/observe.py, DESIGN.md 5s, csrc/obs.hip).  The objective becomes
+ *   mean_b log(w_press * press_b + w_cont * cont_b + w_mom * (mom_x_b + mom_y_b) + w_obs * obs_b).
+ * What is fitted is the network's OWN nodal prediction, phi[:, 0:3] = BC(10 tanh(dec / 10)) (gfv_phi_fwd), before the
+ * cell-to-node smoothing, in the units of the returned uvp_node.  For node i of graph b and channel c in (u, v, p):
+ *   pred = (phi[i, c] * uvp_dim[b, c]) * sigma[b, c]       fp32, the order of gfv_cell_to_node
+ *   e    = pred - target[i, c]                             fp32
+ *   w    = weight[i, c] >= 0                               fp32; an element with w == 0 is skipped BEFORE its target is read into
+ *                                                          any arithmetic: unobserved targets may hold anything, NaN included
+ *   S_b  = sum w * (e * e),  W_b = sum w                   every product and sum in double; per row ((c0 + c1) + c2); per chunk and
+ *                                                          per graph in the fixed order of gfv_rollout_advance (csrc/gfv_reduce.h)
+ *   obs_b = (float)(S_b / W_b), 0 when W_b == 0            divided in double, rounded once
+ *
+ * gfv_obs_fwd: ONE launch behind the forward (one wave per chunk).  partial_ws: 2 doubles per chunk, (S, W); counter: one int32,
+ *   zero before the first launch and left at zero (write-through arrival, csrc/gfv_reduce.h).  The workgroup that arrives last
+ *   writes, with the arithmetic of gfv_fvm_fwd_tail's loss (fp32, 64 strided partial sums of logf folded from the left):
+ *     tot_b = (w_press * press_b + w_cont * cont_b + w_mom * mom_x_b + w_mom * mom_y_b) + w_obs * obs_b      hyper[5..7], *w_obs
+ *     loss[0] = (sum_b logf(tot_b)) / B;  inv_b = 1 / (tot_b * B);  gloss[b] = (w_cont, w_mom, w_mom, w_press) * inv_b
+ *     rec[b] = (obs_b, (float)W_b, gobs_b = w_obs * inv_b, tot_b)                          GFV_OBS_RECORD floats per graph
+ *   loss and gloss are OVERWRITTEN: the launch stands behind the one that formed them from `losses` alone.  w_obs is one device
+ *   float of the caller's: a new value reaches recorded and captured launches without re-recording.
+ * gfv_obs_bwd: ONE launch, one thread per node, between gfv_fvm_bwd_fused / gfv_phi_bwd and the decoder's backward:
+ *     g_dec[i, c] += gobs_b * (2 * w * e * (uvp_dim[b, c] * sigma[b, c]) / W_b) * (1 - tanhf(dec[i, c] / 10)^2)       fp32
+ *   where w != 0 and gfv_phi_bwd lets gradient through (u, v: not at WALL / INFLOW / PRESS / INWALL nodes; p: not at PRESS
+ *   nodes).  No other element is written: with every weight zero g_dec keeps its bits.
+ * gfv_obs_gather: ONE launch (pool path): dst_values / dst_weights [dst_rows, 3] rows off_b .. off_b + rows[b] - 1 (off = the
+ *   running sum of rows) = values[b] / weights[b] [rows[b], 3]; a graph with values[b] == weights[b] == NULL gets zero weights and
+ *   its values are left alone.  values, weights and rows are HOST arrays of B entries (device addresses, row counts): they travel
+ *   by value in the launch's argument block, so the launch is issued per batch and is never part of a recorded list.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, B outside [1, GFV_POOL_MAX_GRAPHS], N or n_chunks < 1 (gfv_obs_bwd: N < 0;
+ * N == 0 launches nothing), a phi or rec that is not 16-byte aligned, a negative row count, only one of values[b] / weights[b]
+ * NULL, or rows that sum to more than dst_rows.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_OBS_RECORD 4
+int gfv_obs_fwd(const float* phi, const float* target, const float* weight, int32_t N, const int32_t* chunk_beg,
+                const int32_t* chunk_end, const int32_t* gchunk_ptr, int32_t n_chunks, int32_t B, const float* uvp_dim,
+                const float* sigma, const float* losses, const float* hyper, const float* w_obs, double* partial_ws,
+                int32_t* counter, float* rec, float* loss, float* gloss, void* stream);
+int gfv_obs_bwd(const float* rec, const float* dec, const float* phi, const float* target, const float* weight,
+                const int32_t* batch, const int32_t* node_type, const float* uvp_dim, const float* sigma, int32_t N, int32_t B,
+                float* g_dec, void* stream);
+int gfv_obs_gather(const float* const* values, const float* const* weights, const int32_t* rows, int32_t B, float* dst_values,
+                   float* dst_weights, int64_t dst_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Evaluation over a device pool (gfv/evaluate.py; the training objective of pre_train_Adam.py:177-184 and field errors on
  * entries that are not trained on).  ONE launch behind the forward-only step of a batch turns its outputs into a record of
  * GFV_EVAL_RECORD floats per graph and writes it to row entry[b] of table [n_entries, GFV_EVAL_RECORD]:
