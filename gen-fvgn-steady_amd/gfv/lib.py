@@ -110,6 +110,8 @@ EVAL_RECORD = 16   # GFV_EVAL_RECORD of include/gfv.h: floats per row of the tab
 TRAIN_LOG_CHUNK, TRAIN_LOG_HEAD, TRAIN_LOG_ENTRY_RECORD, TRAIN_LOG_MAX_BUCKETS = 1024, 16, 8, 32
 # GFV_MARCH_* of include/gfv.h: words of the march record, head words and per-graph words of a history row, the two flags
 MARCH_RECORD, MARCH_HEAD, MARCH_GRAPH, MARCH_CONVERGED, MARCH_CAPPED = 16, 8, 8, 1, 2
+# GFV_FIELD_STATS_* of include/gfv.h: words of the record, planes of the double sums, planes of the float state
+FIELD_STATS_RECORD, FIELD_STATS_SUMS, FIELD_STATS_AUX = 8, 7, 9
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -288,6 +290,7 @@ _SIGNATURES = {
     "gfv_march_advance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                                                      C.c_void_p, C.c_void_p]),
+    "gfv_field_stats_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

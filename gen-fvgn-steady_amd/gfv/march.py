@@ -38,6 +38,12 @@ One batch per object: `set_batch()` is refused.  The march state is not part of 
 With a schedule attached every step issues one more launch in front of the march launch (`gfv_lr_schedule`, mode FOLLOW): the
 schedule's epoch becomes the level count, capped at the last level that runs, and that level's rate is written where Adam reads it.
 The step that ends a level runs at that level's rate; held steps change neither the rate nor the schedule's record.
+
+`field_stats=FieldStats(start=, stride=, stop=)` (gfv/fieldstats.py): one more launch behind the march launch keeps the
+time mean, the variances, u'v' and the extremes of the LEVELS' fields on the device, following the level count: exactly one sample
+per completed level (the field level 0 leaves has clock 1), whatever its inner count; steps that do not end a level, and held
+steps, sample nothing.  `ms.field_stats.read()` reads them; `stats()` keeps its meaning (the march record).  Not part of
+`state_dict()`.  `field_stats=None` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -50,6 +56,7 @@ import struct
 import torch
 
 from . import lib as L
+from .fieldstats import FieldStats
 from .optstep import optimizer_launches
 from .schedule import Plateau
 from .trainer import TrainStep
@@ -129,10 +136,15 @@ def decode_history(words, B):
 
 class MarchStep(TrainStep):
     def __init__(self, model, graphs, *, max_inner=20, min_inner=1, tol=1e-2, abs_tol=None, max_levels=1000, keep=0,
-                 use_graph="list", **trainstep_kwargs):
+                 use_graph="list", field_stats=None, **trainstep_kwargs):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
+        if field_stats is not None and not isinstance(field_stats, FieldStats):
+            raise ValueError(f"MarchStep: field_stats must be a gfv.fieldstats.FieldStats or None, got {field_stats!r}")
+        if field_stats is not None:
+            field_stats.check_free()
         self._march = None
+        self.field_stats = None
         super().__init__(model, graphs, use_graph=use_graph, **trainstep_kwargs)
         self._max_inner, self._min_inner, self._tol, self._abs_tol, self.max_levels, self.keep = args
         dev, pl = self.dev, self.plan
@@ -150,6 +162,9 @@ class MarchStep(TrainStep):
         self._mirror, self._mirror_dev = host, devp.value
         self._write_control()
         self._put(TARGET, [self.max_levels])     # (step() on its own marches until the history is full)
+        if field_stats is not None:
+            # (attached last: the constructor above issues no step, so no list has been recorded without its launch)
+            self.field_stats = field_stats.attach(self, self.x_backup)
 
     def __del__(self):
         host = getattr(self, "_mirror", None)
@@ -218,6 +233,10 @@ class MarchStep(TrainStep):
             self.hyper.data_ptr(), self._march.data_ptr(), self._r0.data_ptr(), self._hist.data_ptr(), self.max_levels,
             self._max_inner, self._min_inner, None if self._snap is None else self._snap.data_ptr(), self.keep, self._mirror_dev,
             L.stream_ptr()), "gfv_march_advance")
+        if self.field_stats is not None:
+            # the clock is the level count: it moves on the launch that ends a level and on no other, so a level is sampled once,
+            # whatever its inner count, and a held step samples nothing
+            self.field_stats.launch(self.x_backup, self._march.data_ptr() + 4 * LEVEL)
 
     def _adam(self):
         optimizer_launches(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper,
@@ -308,7 +327,7 @@ class MarchStep(TrainStep):
 
     def reset(self, x=None):
         """Back to level 0 from the initial node state (or from `x` [N, 12], un-normalised): record, r0, history and snapshots
-        are cleared.  Parameters and optimiser state stay as they are."""
+        are cleared, the field statistics (if any) start over.  Parameters and optimiser state stay as they are."""
         src = self._x0 if x is None else x
         if tuple(src.shape) != tuple(self.x_backup.shape) or not src.is_cuda:
             raise ValueError(f"x must be a device tensor of shape {tuple(self.x_backup.shape)}")
@@ -324,3 +343,5 @@ class MarchStep(TrainStep):
             self._mirror[i] = 0
         self._write_control()
         self._put(TARGET, [self.max_levels])
+        if self.field_stats is not None:
+            self.field_stats.reset()

@@ -35,6 +35,12 @@ the losses and uvp_cell are the model's for the state it was given), history col
 iterates are not time steps of the model: a time-accurate unsteady rollout must leave it off.  The defaults
 `anderson_reg=1e-10` and `anderson_restart=10` are those of a CPU experiment on linear contractions; they have not been tuned on
 a trained model.  `anderson=0` (the default) issues no new launch and allocates nothing.
+
+Field statistics (`field_stats=FieldStats(start=, stride=, stop=)`; gfv/fieldstats.py).  For the UNSTEADY rollout: one
+more launch behind the advance samples the field just written into per-node running sums - time mean, variances, u'v', extremes -
+following the step counter (the field step k leaves has clock k, the first is 1).  Eager steps and recorded lists carry it alike;
+`r.field_stats.read()` is the one synchronisation, `set_window()` moves the window under a recorded list.  Refused together with
+`anderson` > 0.  `field_stats=None` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -43,6 +49,7 @@ import torch
 from . import anderson as AA
 from . import cmdlist
 from . import lib as L
+from .fieldstats import FieldStats
 from .functions import require_gpu
 from .listcache import WARM, ListCache
 from .plan import get_plan
@@ -59,14 +66,27 @@ def check_room(steps_done, max_steps, steps=1):
                          "(the device history has one row per step); reset() or build the Rollout with a larger max_steps")
 
 
+def check_field_stats(field_stats, anderson):
+    """What a Rollout refuses of `field_stats=`; needs no GPU."""
+    if field_stats is None:
+        return
+    if not isinstance(field_stats, FieldStats):
+        raise ValueError(f"field_stats must be a gfv.fieldstats.FieldStats or None, got {field_stats!r}")
+    field_stats.check_free()
+    if anderson:
+        raise ValueError("Rollout: anderson > 0 together with field_stats is not supported (accelerated iterates are not time "
+                         "steps of the model: their mean and variance are not the flow's)")
+
+
 class Rollout:
     WARM = WARM   # eager steps before a list is recorded (they are steps of the rollout like any other)
 
     def __init__(self, model, graphs, max_steps=1000, launch_mode="cmd_list", norm_global=None, anderson=0, anderson_beta=1.0,
-                 anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0):
+                 anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0, field_stats=None):
         if launch_mode not in ("cmd_list", "eager"):
             raise ValueError('launch_mode must be "cmd_list" or "eager"')
         aa_args = AA.check_args(anderson, anderson_beta, anderson_reg, anderson_restart, anderson_start)
+        check_field_stats(field_stats, aa_args[0])
         graph_node = graphs[0]
         x = graph_node.x
         require_gpu(x)
@@ -100,6 +120,8 @@ class Rollout:
         self._lists = ListCache(None, dev=dev)      # accumulate -> the recorded step; unbounded: two keys at most
         self._outs = None
         self._fwd = StaticForward(model, pl.B, dev)
+        # (attached last: should a line above raise, the FieldStats stays free for another owner)
+        self.field_stats = None if field_stats is None else field_stats.attach(self, self.x_backup)
 
     # ---- weights -------------------------------------------------------------------------------------------------------
     def refresh_weights(self):
@@ -120,6 +142,8 @@ class Rollout:
             uvp_node.data_ptr(), self.x_backup.data_ptr(), self.x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(),
             pl.chunk_end.data_ptr(), pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(),
             self.history.data_ptr(), self.max_steps, self._state.data_ptr(), L.stream_ptr()), "gfv_rollout_advance")
+        if self.field_stats is not None:
+            self.field_stats.launch(self.x_backup, self._state.data_ptr())     # (the clock: the step counter just advanced)
         L.status_publish()
         return losses, uvp_node, uvp_cell
 
@@ -164,7 +188,8 @@ class Rollout:
         return self.history[:self.steps_done].cpu()
 
     def reset(self, x=None):
-        """Back to step 0 from the initial node state (or from `x` [N,12], un-normalised); the history is cleared."""
+        """Back to step 0 from the initial node state (or from `x` [N,12], un-normalised); the history is cleared, and the field
+        statistics (if any) start over."""
         src = self._x0 if x is None else x
         if x is not None:
             require_gpu(x)
@@ -176,6 +201,8 @@ class Rollout:
         self._state.zero_()
         if self._aa is not None:
             self._aa.reset()
+        if self.field_stats is not None:
+            self.field_stats.reset()
         self.steps_done = 0
         self._outs = None
 

@@ -1025,6 +1025,46 @@ int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
                       int32_t max_inner, int32_t min_inner, float* snap, int32_t keep, int32_t* mirror_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Field statistics (gfv/fieldstats.py): the time mean, the variances, the Reynolds shear stress u'v' and the
+ * extremes of the node field over a window of a run, kept on the device.  ONE launch behind the launch that has advanced the
+ * field (gfv_rollout_advance, gfv_march_advance), on the same stream.
+ *   x_backup   [N, 12] float, 16-byte aligned: columns 0:3 of a row are the field (u, v, p); nothing else of a row is used
+ *   clock      the device address of one int32 that increases whenever a new field has been written: word 0 of
+ *              gfv_rollout_advance's state, word [6] `level` of gfv_march_advance's record (the idea of GFV_SCHED_FOLLOW)
+ *   rec        GFV_FIELD_STATS_RECORD 32-bit words of the caller's:
+ *     [0] start    (int32, host)    the first clock value to sample
+ *     [1] stride   (int32, host)    sampling stride; values < 1 are read as 1
+ *     [2] stop     (int32, host)    exclusive end; negative: none
+ *     [3] last     (int32)          the clock value the last launch found; -1 after a reset
+ *     [4] n        (int32)          samples taken
+ *     [5]          (int32)          arrival counter, zero between launches
+ *     [6] enabled  (int32, host)    0 pauses sampling
+ *     [7]                           zero
+ *   sums       double [GFV_FIELD_STATS_SUMS, N], planar: S1u, S1v, S1p, S2uu, S2vv, S2pp, S2uv
+ *   aux        float [GFV_FIELD_STATS_AUX, N], planar: the shift K of u, v, p; the minimum of u, v, p; the maximum of u, v, p
+ * The rule, with the record AS THE LAUNCH FINDS IT (every workgroup reads it and *clock before anything is written; the
+ * workgroup that arrives last writes it):
+ *   c = *clock
+ *   take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % stride == 0
+ *   take false:  no row and no element of sums or aux is read or written
+ *   take true, per row, x the row's three floats:
+ *     n == 0:    K = min = max = x; all seven sums are written as +0.0 (so a reset is last = -1, n = 0: no memset)
+ *     n > 0:     d = (double)x - (double)K per channel; S1 += d; S2uu += du * du; S2vv += dv * dv; S2pp += dp * dp;
+ *                S2uv += du * dv - each product and each sum ONE IEEE double operation, nothing contracted;
+ *                min = fminf(min, x); max = fmaxf(max, x) (a NaN sample leaves them; a NaN they hold is replaced)
+ *   then:        last = c if it differs; n += 1 if take; the counter back to 0
+ * So mean = K + S1 / n, the population variance S2 / n - (S1 / n)^2, cov(u, v) = S2uv / n - (S1u / n)(S1v / n): shifted by the
+ * first sample, the sums stay of the size of the fluctuation.  No floating-point atomics and no sum across rows: the same
+ * inputs give the same bits, whatever the grid.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, N < 1 or an x_backup that is not 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_FIELD_STATS_RECORD 8
+#define GFV_FIELD_STATS_SUMS 7
+#define GFV_FIELD_STATS_AUX 9
+int gfv_field_stats_update(const float* x_backup, int32_t N, const int32_t* clock, int32_t* rec, double* sums, float* aux,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
  * at pre_train_Adam.py:203 and solve_with_grad_GPU.py:197, and torch.optim.lr_scheduler.ReduceLROnPlateau).  ONE launch of one
  * wave recomputes the rate from a device record and writes it where the Adam launches read it:
