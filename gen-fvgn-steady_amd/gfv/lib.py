@@ -112,6 +112,10 @@ TRAIN_LOG_CHUNK, TRAIN_LOG_HEAD, TRAIN_LOG_ENTRY_RECORD, TRAIN_LOG_MAX_BUCKETS =
 MARCH_RECORD, MARCH_HEAD, MARCH_GRAPH, MARCH_CONVERGED, MARCH_CAPPED = 16, 8, 8, 1, 2
 # GFV_FIELD_STATS_* of include/gfv.h: words of the record, planes of the double sums, planes of the float state
 FIELD_STATS_RECORD, FIELD_STATS_SUMS, FIELD_STATS_AUX = 8, 7, 9
+# GFV_TIME_BC_* of include/gfv.h: doubles of a waveform record, words of the control record, doubles of a history row, points of a
+# table at most, the kinds of gfv_time_bc_update
+TIME_BC_RECORD, TIME_BC_CTL, TIME_BC_HIST, TIME_BC_TABLE_MAX = 8, 4, 3, 1024
+TIME_BC_NONE, TIME_BC_CONST, TIME_BC_RAMP_LINEAR, TIME_BC_RAMP_SMOOTH, TIME_BC_SINE, TIME_BC_TABLE, TIME_BC_TABLE_PERIODIC = range(7)
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -291,6 +295,8 @@ _SIGNATURES = {
                                     C.c_int32] + [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                                                      C.c_void_p, C.c_void_p]),
     "gfv_field_stats_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gfv_time_bc_update": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
+                           + [C.c_int32] * 3 + [C.c_void_p]),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

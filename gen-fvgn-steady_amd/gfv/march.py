@@ -44,6 +44,14 @@ time mean, the variances, u'v' and the extremes of the LEVELS' fields on the dev
 per completed level (the field level 0 leaves has clock 1), whatever its inner count; steps that do not end a level, and held
 steps, sample nothing.  `ms.field_stats.read()` reads them; `stats()` keeps its meaning (the march record).  Not part of
 `state_dict()`.  `field_stats=None` (the default) issues no new launch and allocates nothing.
+
+`time_bc=TimeBC(velocity=, source=, nodes=)` (gfv/timebc.py): one more launch behind the march launch rewrites the
+Dirichlet velocity targets and the source coefficient for the level about to be computed (level count + 1), from per-graph waveform
+records on the device.  The host cannot do this: only the device knows which step starts a new level.  Inner iterations and held
+steps find the level count they found before and write the same values again.  With it `state_dict()` carries the level count
+(`gfv_time_bc`: one synchronisation) and `load_state_dict()` puts the boundary data of the level that comes next in place, so a
+march that resumes in a new object is driven as the uninterrupted one.  `time_bc=None` (the default) issues no new launch and
+allocates nothing.
 """
 from __future__ import annotations
 
@@ -56,6 +64,7 @@ import struct
 import torch
 
 from . import lib as L
+from . import timebc as TB
 from .fieldstats import FieldStats
 from .optstep import optimizer_launches
 from .schedule import Plateau
@@ -136,15 +145,17 @@ def decode_history(words, B):
 
 class MarchStep(TrainStep):
     def __init__(self, model, graphs, *, max_inner=20, min_inner=1, tol=1e-2, abs_tol=None, max_levels=1000, keep=0,
-                 use_graph="list", field_stats=None, **trainstep_kwargs):
+                 use_graph="list", field_stats=None, time_bc=None, **trainstep_kwargs):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
         if field_stats is not None and not isinstance(field_stats, FieldStats):
             raise ValueError(f"MarchStep: field_stats must be a gfv.fieldstats.FieldStats or None, got {field_stats!r}")
         if field_stats is not None:
             field_stats.check_free()
+        TB.check_owner(time_bc, graphs)
         self._march = None
         self.field_stats = None
+        self.time_bc = None
         super().__init__(model, graphs, use_graph=use_graph, **trainstep_kwargs)
         self._max_inner, self._min_inner, self._tol, self._abs_tol, self.max_levels, self.keep = args
         dev, pl = self.dev, self.plan
@@ -165,6 +176,9 @@ class MarchStep(TrainStep):
         if field_stats is not None:
             # (attached last: the constructor above issues no step, so no list has been recorded without its launch)
             self.field_stats = field_stats.attach(self, self.x_backup)
+        if time_bc is not None:
+            # (its attach issues the launch for level 0's field: the level count is 0)
+            self.time_bc = time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._march, LEVEL, self.max_levels)
 
     def __del__(self):
         host = getattr(self, "_mirror", None)
@@ -237,6 +251,10 @@ class MarchStep(TrainStep):
             # the clock is the level count: it moves on the launch that ends a level and on no other, so a level is sampled once,
             # whatever its inner count, and a held step samples nothing
             self.field_stats.launch(self.x_backup, self._march.data_ptr() + 4 * LEVEL)
+        if self.time_bc is not None:
+            # the targets of level count + 1: new values behind the launch that ended a level, the same values again behind an inner
+            # iteration or a held step (an early-out would need the blocks to agree on a "last" word: DESIGN.md 5u)
+            self.time_bc.launch()
 
     def _adam(self):
         optimizer_launches(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper,
@@ -345,3 +363,27 @@ class MarchStep(TrainStep):
         self._put(TARGET, [self.max_levels])
         if self.field_stats is not None:
             self.field_stats.reset()
+        if self.time_bc is not None:
+            self.time_bc.reset()                      # (behind the record's zero: the data of level 0's field)
+
+    # ---- checkpoints -----------------------------------------------------------------------------------------------------------
+    def state_dict(self):
+        """TrainStep's; with `time_bc` also the time the boundary data have reached: `gfv_time_bc` = {"clock": levels completed,
+        this object's clock offset included} (one synchronisation).  The march record itself is not part of it."""
+        sd = super().state_dict()
+        if self.time_bc is not None:
+            sd["gfv_time_bc"] = {"clock": self._read_record()[LEVEL] + self.time_bc.clock_offset}
+        return sd
+
+    def load_state_dict(self, sd):
+        """TrainStep's; with `time_bc` the boundary data of the level that comes next are put in place: clock = the saved count + 1
+        (a dict without `gfv_time_bc`: this object's own level count + 1).  The field itself is the caller's to carry over
+        (`graphs[0].x` of the new object, or `reset(x=)` before loading)."""
+        super().load_state_dict(sd)
+        if self.time_bc is not None:
+            saved = sd.get("gfv_time_bc")
+            level = self._read_record()[LEVEL]
+            clock = level if saved is None else int(saved["clock"])
+            if clock < level:
+                raise ValueError(f"the saved boundary-data clock {clock} lies before this object's level count {level}")
+            self.time_bc.set_clock_offset(clock - level)

@@ -1065,6 +1065,62 @@ int gfv_field_stats_update(const float* x_backup, int32_t N, const int32_t* cloc
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Unsteady boundary data (gfv/timebc.py): the Dirichlet velocity targets and the source coefficient as functions
+ * of time, rewritten for the field about to be computed.  ONE launch behind the launch that has advanced the field
+ * (gfv_rollout_advance, gfv_march_advance), on the same stream.
+ *   clock      the device address of one int32 counting the fields written so far (gfv_field_stats_update's clock)
+ *   ctl        GFV_TIME_BC_CTL int32 words of the caller's: [0] offset (host) added to the clock; the rest zero
+ *   rec        double [B, 2, GFV_TIME_BC_RECORD], 8-byte aligned: per graph the velocity waveform's record, then the source's:
+ *     d[0] kind   GFV_TIME_BC_NONE .. GFV_TIME_BC_TABLE_PERIODIC (a whole number)
+ *     CONST:        d[1] value
+ *     RAMP_*:       d[1] g0, d[2] g1, d[3] t0, d[4] t1 (t1 > t0)
+ *     SINE:         d[1] mean, d[2] amp, d[3] freq, d[4] phase, d[5] start
+ *     TABLE*:       d[1] n, 1 .. GFV_TIME_BC_TABLE_MAX points (PERIODIC: at least 2) in the record's slot of `tab`
+ *   tab        double [B, 2, 2, GFV_TIME_BC_TABLE_MAX]: per record its times (strictly increasing), then its values; NULL when no
+ *              record is a table
+ *   dt         float [B];  batch, node_type  int32 [N]
+ *   y0, y      float [N, 2], 8-byte aligned, distinct: the base targets (read) and the targets the forward reads (written)
+ *   theta0     float [B]: the base source coefficient;  theta5: the address of element (0, 5) of the coefficient table the forward
+ *              reads, ld_theta floats per graph
+ *   x_backup, x  float [N, 12] or NULL: node-feature column 8 (= 3 + 5) of every row takes the value written to theta5
+ *   hist       double [K_max, B, GFV_TIME_BC_HIST] or NULL: row c - 1 = (t, g_v, g_s) per graph, written for 1 <= c <= K_max
+ *   type_mask  bit k set: rows of node type k (0 .. 5) take the velocity waveform
+ *   channels   bit 0: the velocity channel, bit 1: the source channel; a channel that is off writes nothing (its g is recorded as 1)
+ * With c = *clock + 1 + ctl[0] and, per graph b, t = (double)c * (double)dt[b] - every operation below ONE IEEE double operation
+ * in the order written, nothing contracted:
+ *   CONST         g = value
+ *   RAMP_LINEAR   s = min(max((t - t0) / (t1 - t0), 0), 1);  g = g0 + (g1 - g0) * s
+ *   RAMP_SMOOTH   s as above;  g = g0 + (g1 - g0) * ((s * s) * (3 - 2 * s))
+ *   SINE          g = mean + amp * sin(((2 pi * freq) * max(t - start, 0)) + phase)    (2 pi: the double 6.283185307179586; sin
+ *                 is the device library's: within DESIGN.md 5u's measured distance of the correctly rounded value)
+ *   TABLE         t <= T[0]: V[0];  t >= T[n-1]: V[n-1];  else with T[k] <= t < T[k+1]:
+ *                 g = V[k] + (V[k+1] - V[k]) * ((t - T[k]) / (T[k+1] - T[k]))
+ *   TABLE_PERIODIC  m = fmod(t - T[0], T[n-1] - T[0]); m += T[n-1] - T[0] if m < 0;  t = T[0] + m;  then as TABLE
+ *   row i of graph b, node_type[i] in the mask, velocity on:   y[i, 0:2] = (float)(g_v * (double)y0[i, 0:2])
+ *   every row i of graph b, source on:                         x_backup[i, 8] = x[i, 8] = (float)(g_s * (double)theta0[b])
+ *   per graph:                                                 theta5[b * ld_theta] = the same float; the history row
+ * Every other element is left as it is.  Nothing written is read: a launch that finds the same clock writes the same bits.
+ * GFV_ERR_ARG (nothing launched) on a NULL clock, ctl, rec, dt, batch or node_type, N or B < 1, channels outside 1 .. 3, a
+ * type_mask beyond bit 5, the velocity channel without y0 / y (or y0 == y, or either not 8-byte aligned), the source channel
+ * without theta0 / theta5 or ld_theta < 1, hist with K_max < 1, or a rec / tab / hist that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_TIME_BC_RECORD 8
+#define GFV_TIME_BC_CTL 4
+#define GFV_TIME_BC_HIST 3
+#define GFV_TIME_BC_TABLE_MAX 1024
+#define GFV_TIME_BC_NONE 0
+#define GFV_TIME_BC_CONST 1
+#define GFV_TIME_BC_RAMP_LINEAR 2
+#define GFV_TIME_BC_RAMP_SMOOTH 3
+#define GFV_TIME_BC_SINE 4
+#define GFV_TIME_BC_TABLE 5
+#define GFV_TIME_BC_TABLE_PERIODIC 6
+int gfv_time_bc_update(const int32_t* clock, const int32_t* ctl, const double* rec, const double* tab, const float* dt,
+                       const int32_t* batch, const int32_t* node_type, int32_t N, int32_t B, const float* y0, float* y,
+                       const float* theta0, float* theta5, int32_t ld_theta, float* x_backup, float* x, double* hist,
+                       int32_t K_max, int32_t type_mask, int32_t channels, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
  * at pre_train_Adam.py:203 and solve_with_grad_GPU.py:197, and torch.optim.lr_scheduler.ReduceLROnPlateau).  ONE launch of one
  * wave recomputes the rate from a device record and writes it where the Adam launches read it:
