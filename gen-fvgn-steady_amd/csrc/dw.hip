@@ -666,7 +666,12 @@ extern "C" int gfv_dw_slabs(int32_t M, int32_t ntiles, int32_t* rows_per_slab) {
 extern "C" int gfv_dw_multi(const gfv_dw_tile_t* tiles, int32_t ntiles, int32_t M, int64_t block_floats, float* workspace,
                             float* grad_block, int32_t accumulate, void* stream) {
   if (ntiles < 1 || ntiles > 6 || M < 0 || block_floats <= 0) return GFV_ERR_ARG;
-  if (M == 0) return GFV_OK;
+  if (M == 0) {
+    // no rows, no slabs: nothing is launched and the workspace is not read.  accumulate = 0 still owes the caller a written
+    // block (zeros: a sum over no chunks), accumulate = 1 leaves it as it is
+    if (grad_block && !accumulate) return gfv_reduce_partials(workspace, 0, (int32_t)block_floats, grad_block, 0, stream);
+    return GFV_OK;
+  }
   DwLaunch a;
   double fl = 0, by = 0;
   for (int i = 0; i < ntiles; ++i) {
@@ -738,6 +743,14 @@ extern "C" int gfv_linear_dw_gs(const float* G, int32_t ldg, int32_t n_out, cons
     t[i].db_off = (i == 0 && db) ? wfl : -1;
     t[i].gscale = gscale;
     koff += segs[i].width;
+  }
+  if (M == 0) {
+    // no slab was written and no reduced block exists: zeros (a sum over no chunks) or, accumulating, nothing - the
+    // workspace is not read (it used to be reduced into dW / db as it was found)
+    if (accumulate) return GFV_OK;
+    int rc0 = gfv_reduce_partials(workspace, 0, (int32_t)wfl, dW, 0, stream);
+    if (!rc0 && db) rc0 = gfv_reduce_partials(workspace, 0, n_out, db, 0, stream);
+    return rc0;
   }
   const int slabs = gfv_dw_slabs(M, nseg, nullptr);
   float* tmp = workspace + (size_t)slabs * block;  // reduced block, then split into dW / db

@@ -302,6 +302,8 @@ int gfv_weight_images_form(const float* wmax);
 /* Weight gradient of a Linear layer: dW[n,k] = sum_m G[m,n] * A[m,k], db[n] = sum_m G[m,n] (two-stage,
  * deterministic).  A is assembled like the forward input (segments, gather, optional GELU of a saved
  * pre-activation).  partial: workspace [gfv_dw_chunks(M), N(=128), Kpad] (+ N floats per chunk for db).
+ * M = 0 (no rows) is legal: accumulate = 0 writes zeros to dW and db, accumulate = 1 leaves them unchanged; nothing else is
+ * launched and the workspace is neither read nor written.
  * Replaces the autograd mm/addmm wgrad of nn.Linear (pre_train_Adam.py:188). */
 int gfv_dw_chunks(int32_t M);
 int gfv_linear_dw(const float* G, int32_t ldg, int32_t n_out, const gfv_seg_t* segs, int32_t nseg,
@@ -322,7 +324,9 @@ int gfv_linear_dw_ex(const float* G, int32_t ldg, int32_t n_out, const gfv_seg_t
  * block[out_off + n*ld_out + k]; if db_off >= 0 also block[db_off + n] = sum_m G_t[m,n].  `grad_block` is the
  * contiguous gradient storage of the parameter block ([W1|b1|W2|b2|W3|b3] in state_dict order, each tensor padded
  * to a multiple of 4 floats), block_floats its length.  workspace: gfv_dw_multi_workspace_floats(...) floats,
- * zero-initialised once by the caller (padding slots are never written). */
+ * zero-initialised once by the caller (padding slots are never written).
+ * M = 0: the workspace is not touched; a grad_block is zeroed (all block_floats of it) with accumulate = 0 and left unchanged with
+ * accumulate = 1; with grad_block == NULL there are no slabs (gfv_dw_slabs returns 0) and nothing for the caller to reduce. */
 typedef struct {
   const float* G;       /* [M, ldg] upstream gradient rows */
   const float* A;       /* input rows [*, ld] */
