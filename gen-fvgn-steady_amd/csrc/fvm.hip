@@ -36,6 +36,28 @@ __global__ __launch_bounds__(256) void phi_fwd_kernel(const float* __restrict__ 
   o[1] = make_float4(vh, uo, vo, 0.f);
 }
 
+// phi_fwd_kernel with a time scheme attached (gfv/timescheme.py): uv_hat from uv_old (u_n) as above, channels 5,6 = uv_star, the
+// baseline of the time difference.  A kernel of its own: the one above compiles as it did.
+__global__ __launch_bounds__(256) void phi_fwd_ts_kernel(const float* __restrict__ dec, const float* __restrict__ y,
+                                                         const int* __restrict__ node_type, const float* __restrict__ uv_old,
+                                                         const float* __restrict__ uv_star, float* __restrict__ phi, int N,
+                                                         int mode) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= N) return;
+  const int nt = node_type[i];
+  float u = tanhf(dec[3 * i] / 10.f) * 10.f, v = tanhf(dec[3 * i + 1] / 10.f) * 10.f, p = tanhf(dec[3 * i + 2] / 10.f) * 10.f;
+  if (nt == NT_WALL || nt == NT_INFLOW || nt == NT_PRESS || nt == NT_INWALL) { u = y[2 * i]; v = y[2 * i + 1]; }
+  if (nt == NT_PRESS) p = 0.f;
+  const float uo = uv_old[2 * i], vo = uv_old[2 * i + 1];
+  float uh, vh;
+  if (mode == 0) { uh = uo; vh = vo; }
+  else if (mode == 1) { uh = u; vh = v; }
+  else { uh = (uo + u) / 2.0f; vh = (vo + v) / 2.0f; }
+  float4* o = reinterpret_cast<float4*>(phi + (size_t)i * 8);
+  o[0] = make_float4(u, v, p, uh);
+  o[1] = make_float4(vh, uv_star[2 * i], uv_star[2 * i + 1], 0.f);
+}
+
 __global__ __launch_bounds__(256) void phi_bwd_kernel(const float* __restrict__ gphi, const float* __restrict__ dec,
                                                       const int* __restrict__ node_type, float* __restrict__ gdec, int N,
                                                       int mode) {
@@ -1059,6 +1081,14 @@ extern "C" int gfv_phi_fwd(const float* dec, const float* y, const int32_t* node
                            int32_t N, int32_t mode, void* stream) {
   GfvProfScope ps_(GFV_K_FVM, 0, 56.0 * N, stream);
   LAUNCH1D(phi_fwd_kernel, N, stream, dec, y, node_type, uv_old, phi, N, mode);
+  return GFV_OK;
+}
+
+extern "C" int gfv_phi_fwd_ts(const float* dec, const float* y, const int32_t* node_type, const float* uv_old,
+                              const float* uv_star, float* phi, int32_t N, int32_t mode, void* stream) {
+  if (!dec || !y || !node_type || !uv_old || !uv_star || !phi) return GFV_ERR_ARG;
+  GfvProfScope ps_(GFV_K_FVM, 0, 64.0 * N, stream);
+  LAUNCH1D(phi_fwd_ts_kernel, N, stream, dec, y, node_type, uv_old, uv_star, phi, N, mode);
   return GFV_OK;
 }
 

@@ -27,6 +27,20 @@ def _empty(dev, *shape):
     return torch.empty(shape, dtype=torch.float32, device=dev)
 
 
+def _check_time_state(time_state, pl, dev):
+    """(ustar [N,2], dt_eff [B]) as the finite-volume section reads them: contiguous float32 device tensors."""
+    try:
+        ustar, dt = time_state
+    except (TypeError, ValueError):
+        raise ValueError("time_state must be a pair (ustar [N, 2], dt_eff [B]) of device tensors") from None
+    for name, t, shape in (("ustar", ustar, (pl.N, 2)), ("dt_eff", dt, (pl.B,))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError(f"time_state: {name} must be a contiguous float32 tensor of shape {shape}")
+        if t.device != dev:
+            raise ValueError(f"time_state: {name} lives on {t.device}, the decoder output on {dev}")
+    return ustar, dt
+
+
 def pick_concurrent_stream(priority=0, candidates=8):
     """A stream that really runs beside the current one.  The HIP runtime multiplexes streams onto a few hardware queues
     (GPU_MAX_HW_QUEUES, default 4) round-robin in creation order, and two streams on one hardware queue execute in order:
@@ -1148,34 +1162,47 @@ class Engine:
     # ------------------------------------------------------------------------------------------------------------
     # finite-volume integrator (FVscheme.py:618-724 -> conserved_form :50-274)
     # ------------------------------------------------------------------------------------------------------------
-    def fvm_fwd(self, dec, uv_old, pl, want_outputs=True, train_loss=None, keep=True):
+    def fvm_fwd(self, dec, uv_old, pl, want_outputs=True, train_loss=None, keep=True, time_state=None):
+        """time_state = (ustar [N,2], dt_eff [B]) of a gfv.timescheme.TimeScheme: channels 5,6 of phi carry `ustar` in place of
+        `uv_old` (uv_hat is still formed from `uv_old`) and the time term's step is `dt_eff` in place of the plan's dt, here and in
+        the adjoint (`fvm_bwd` finds it in the saved state).  None: every launch and every argument as without the keyword."""
         lib = L.load()
         st = L.stream_ptr()
         N, E, C, B = pl.N, pl.E, pl.C, pl.B
         dev = dec.device
         phi = _empty(dev, N, 8)
-        L.check(lib.gfv_phi_fwd(dec.data_ptr(), pl.y.data_ptr(), pl.node_type.data_ptr(), uv_old.data_ptr(), phi.data_ptr(),
-                                N, self.mode, st), "phi_fwd")
-        losses, uvp_node, uvp_cell, sv = self.fvm_core_fwd(phi, pl, want_outputs, train_loss=train_loss, keep=keep)
+        dt = None
+        if time_state is None:
+            L.check(lib.gfv_phi_fwd(dec.data_ptr(), pl.y.data_ptr(), pl.node_type.data_ptr(), uv_old.data_ptr(), phi.data_ptr(),
+                                    N, self.mode, st), "phi_fwd")
+        else:
+            ustar, dt = _check_time_state(time_state, pl, dev)
+            L.check(lib.gfv_phi_fwd_ts(dec.data_ptr(), pl.y.data_ptr(), pl.node_type.data_ptr(), uv_old.data_ptr(),
+                                       ustar.data_ptr(), phi.data_ptr(), N, self.mode, st), "phi_fwd_ts")
+        losses, uvp_node, uvp_cell, sv = self.fvm_core_fwd(phi, pl, want_outputs, train_loss=train_loss, keep=keep, dt=dt)
         if keep:
             sv["dec"] = dec
         return losses, uvp_node, uvp_cell, sv
 
-    def _fvm_mesh(self, pl, raw=False):
-        """gfv_fvm_mesh_t of a plan (include/gfv.h), built once per plan and output mode and kept on it."""
+    def _fvm_mesh(self, pl, raw=False, dt=None):
+        """gfv_fvm_mesh_t of a plan (include/gfv.h), built once per plan, output mode and step tensor and kept on it.  dt: the [B]
+        step of a time scheme (None: the plan's); its address is part of the key, so an object with a scheme and one without that
+        share a plan never get each other's struct."""
         cache = pl.__dict__.setdefault("_fvm_mesh_cache", {})
-        key = (self.mode, self.smooth, self.order_terms, bool(raw))
+        dt = pl.dt if dt is None else dt
+        key = (self.mode, self.smooth, self.order_terms, bool(raw), dt.data_ptr())
         m = cache.get(key)
         if m is None:
             m = L.FvmMesh(N=pl.N, E=pl.E, C=pl.C, B=pl.B, terms=pl.M, mode=self.mode, smooth=self.smooth | (2 if raw else 0), reserved=0)
             for name, t in (("node_type", pl.node_type), ("batch", pl.batch), ("ftype", pl.ftype), ("cbatch", pl.cbatch),
                             ("gcell_ptr", pl.gcell_ptr), ("pos", pl.pos), ("fpos", pl.fpos), ("y", pl.y), ("centroid", pl.centroid),
-                            ("area", pl.area), ("theta", pl.theta), ("sigma", pl.sigma), ("uvp_dim", pl.uvp_dim), ("dt", pl.dt),
+                            ("area", pl.area), ("theta", pl.theta), ("sigma", pl.sigma), ("uvp_dim", pl.uvp_dim), ("dt", dt),
                             ("crow", pl.crow), ("kcell", pl.kcell), ("kS", pl.kS), ("frow", pl.frow), ("fk", pl.fk),
                             ("nfrow", pl.n_rowptr), ("nfcol2", pl.n_col_edge2), ("nrow", pl.nrow), ("ncell", pl.ncell),
                             ("An", pl.An), ("rn", pl.rn), ("xo_rowptr", pl.xo_rowptr), ("xo_in", pl.xo_in), ("xo_B", pl.xo_B),
                             ("sumB", pl.sumB)):
                 setattr(m, name, t.data_ptr())
+            m._dt = dt                       # (the struct holds its address: keep the tensor alive as long as the struct)
             cache[key] = m
         return m
 
@@ -1184,7 +1211,7 @@ class Engine:
             self._fvm_cnt = torch.zeros(4, dtype=torch.int32, device=dev)   # (arrival counter of the tail launch: zero between launches)
         return self._fvm_cnt
 
-    def fvm_core_fwd(self, phi, pl, want_outputs=True, raw_outputs=False, train_loss=None, keep=True):
+    def fvm_core_fwd(self, phi, pl, want_outputs=True, raw_outputs=False, train_loss=None, keep=True, dt=None):
         """phi [N,8] = (uvp_new, uv_hat, uv_old, 0) -> residual losses [B,4], smoothed node field, cell field.
         train_loss = (hyper [8], loss [1], gloss [B,4]) device tensors: the training loss of pre_train_Adam.py:177-184 and its
         gradient with respect to the four residuals are formed behind the residual norms (TrainStep).
@@ -1192,11 +1219,13 @@ class Engine:
         smoothed node field before the Dirichlet overwrite and neither field re-dimensionalised (importer.py:223-231 does both
         afterwards).
         keep=False: forward only - grad, Ff, phic and cres are temporaries of this call (each is read by a later launch of it),
-        the squared residual norms `sums` are not written, None comes back for the saved state."""
+        the squared residual norms `sums` are not written, None comes back for the saved state.
+        dt: the [B] step of the time term (a time scheme's dt_eff); None: the plan's."""
         lib = L.load()
         st = L.stream_ptr()
         N, E, C, B = pl.N, pl.E, pl.C, pl.B
         dev = phi.device
+        dt_t = pl.dt if dt is None else dt
         grad = _empty(dev, N, 16)
         # pl.M: Taylor terms of the reconstruction order the mesh's moment matrices were built for (2 / 5 / 9 / 14)
         if pl.M != self.order_terms:
@@ -1213,7 +1242,7 @@ class Engine:
         L.check(lib.gfv_cell_fwd_ex(phi.data_ptr(), grad.data_ptr(), Ff.data_ptr(), pl.pos.data_ptr(), pl.crow.data_ptr(),
                                     pl.kface.data_ptr(), pl.knode.data_ptr(), pl.kS.data_ptr(), pl.ftype.data_ptr(),
                                     pl.centroid.data_ptr(), pl.area.data_ptr(), pl.cbatch.data_ptr(), pl.theta.data_ptr(),
-                                    pl.dt.data_ptr(), pl.uvp_dim.data_ptr(), pl.sigma.data_ptr(), phic.data_ptr(),
+                                    dt_t.data_ptr(), pl.uvp_dim.data_ptr(), pl.sigma.data_ptr(), phic.data_ptr(),
                                     cres.data_ptr(), None if uvp_cell is None else uvp_cell.data_ptr(), C, self.nc,
                                     None if gradc is None else gradc.data_ptr(), st), "cell_fwd")
         sums, losses = (_empty(dev, B, 4) if (keep or not self._fvm_fuse) else None), _empty(dev, B, 4)
@@ -1224,7 +1253,7 @@ class Engine:
             # residual norms + (train: the training loss and its gradient, by the workgroup that sees the last graph's norms) +
             # node smoothing as ONE launch (round 6, csrc/fvm.hip fvm_tail_kernel)
             tl = train_loss
-            L.check(lib.gfv_fvm_fwd_tail(self._fvm_mesh(pl, raw_outputs), cres.data_ptr(), phic.data_ptr(), phi.data_ptr(),
+            L.check(lib.gfv_fvm_fwd_tail(self._fvm_mesh(pl, raw_outputs, dt), cres.data_ptr(), phic.data_ptr(), phi.data_ptr(),
                                          L.ptr(sums), losses.data_ptr(), None if uvp_node is None else uvp_node.data_ptr(),
                                          None if tl is None else tl[0].data_ptr(), None if tl is None else tl[1].data_ptr(),
                                          None if tl is None else tl[2].data_ptr(), self._fvm_counter(dev).data_ptr(), st), "fvm_fwd_tail")
@@ -1244,6 +1273,8 @@ class Engine:
         if not keep:
             return losses, uvp_node, uvp_cell, None
         sv = dict(Ff=Ff, cres=cres, sums=sums, phi=phi, grad=grad, phic=phic, gradc=gradc)
+        if dt is not None:
+            sv["dt"] = dt                    # (the adjoint's time-term coefficient is formed with the same step)
         return losses, uvp_node, uvp_cell, sv
 
     def fvm_bwd(self, sv, gloss, pl):
@@ -1253,7 +1284,7 @@ class Engine:
             dev = gloss.device
             gFf, gphi, grhs = _empty(dev, pl.E, 16), _empty(dev, pl.N, 8), _empty(dev, pl.N, 8, pl.M)
             gdec = _empty(dev, pl.N, 3)
-            L.check(lib.gfv_fvm_bwd_fused(self._fvm_mesh(pl), sv["cres"].data_ptr(), sv["sums"].data_ptr(), gloss.data_ptr(),
+            L.check(lib.gfv_fvm_bwd_fused(self._fvm_mesh(pl, dt=sv.get("dt")), sv["cres"].data_ptr(), sv["sums"].data_ptr(), gloss.data_ptr(),
                                           sv["Ff"].data_ptr(), sv["dec"].data_ptr(), gFf.data_ptr(), gphi.data_ptr(), grhs.data_ptr(),
                                           gdec.data_ptr(), L.stream_ptr()), "fvm_bwd_fused")
             return gdec
@@ -1272,7 +1303,7 @@ class Engine:
         gc, gFf = _empty(dev, C, 4), _empty(dev, E, 16)
         gphi, ggrad = _empty(dev, N, 8), _empty(dev, N, 16)
         L.check(lib.gfv_fvm_bwd_ex(sv["cres"].data_ptr(), sv["sums"].data_ptr(), gloss.data_ptr(), sv["Ff"].data_ptr(),
-                                pl.cbatch.data_ptr(), pl.theta.data_ptr(), pl.sigma.data_ptr(), pl.dt.data_ptr(),
+                                pl.cbatch.data_ptr(), pl.theta.data_ptr(), pl.sigma.data_ptr(), sv.get("dt", pl.dt).data_ptr(),
                                 pl.frow.data_ptr(), pl.fk.data_ptr(), pl.kcell.data_ptr(), pl.kS.data_ptr(),
                                 pl.ftype.data_ptr(), pl.n_rowptr.data_ptr(), pl.n_col_edge2.data_ptr(), pl.nrow.data_ptr(),
                                 pl.ncell.data_ptr(), pl.crow.data_ptr(), pl.pos.data_ptr(), pl.fpos.data_ptr(),
@@ -1454,7 +1485,7 @@ class Engine:
     # whole model (importer.py:156-240)
     # ------------------------------------------------------------------------------------------------------------
     def forward(self, P, buffers, x, pl, *, norm_global=True, accumulate=True, want_outputs=True, want_edge_attr15=True,
-                before_prep=None, x_raw=None, train_loss=None, keep=True, static_weights=False):
+                before_prep=None, x_raw=None, train_loss=None, keep=True, static_weights=False, time_state=None):
         """keep=False: the forward-only step (gfv/rollout.py, NNmodel.forward under torch.no_grad()) - the same launches on the same
         kernel families with the same arguments except the save pointers, which are NULL wherever no later launch of this forward
         reads the tensor; the outputs have the bits of the saving forward's, None comes back for the saved state.
@@ -1462,7 +1493,8 @@ class Engine:
         vouches that they have not changed: no maximum, no image build in this call, the images stay valid after it.
         before_prep: main-stream work of the caller that only the input preparation waits for (TrainStep's restore of the
         un-normalised node state): issued BEHIND the fork, so that the side stream's image build - which the first encoder launch
-        waits for, ~16 us in round 5's timelines - starts a copy and a cross-queue signal earlier."""
+        waits for, ~16 us in round 5's timelines - starts a copy and a cross-queue signal earlier.
+        time_state: (ustar, dt_eff) of a gfv.timescheme.TimeScheme for the finite-volume section (`fvm_fwd`); None: no change."""
         if static_weights:
             prev = self._wi_static_enter(P)
         else:
@@ -1483,7 +1515,8 @@ class Engine:
                 ops.set_weight_images(prev)
         if not keep:
             del ea16
-        losses, uvp_node, uvp_cell, sv_fvm = self.fvm_fwd(dec, uv_old, pl, want_outputs, train_loss=train_loss, keep=keep)
+        losses, uvp_node, uvp_cell, sv_fvm = self.fvm_fwd(dec, uv_old, pl, want_outputs, train_loss=train_loss, keep=keep,
+                                                             time_state=time_state)
         return losses, uvp_node, uvp_cell, ea15, (dict(sim=sv_sim, fvm=sv_fvm) if keep else None)
 
     def backward(self, P, ctx, gloss, grads, pl, g_dec_hook=None):

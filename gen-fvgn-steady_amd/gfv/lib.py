@@ -116,6 +116,8 @@ FIELD_STATS_RECORD, FIELD_STATS_SUMS, FIELD_STATS_AUX = 8, 7, 9
 # table at most, the kinds of gfv_time_bc_update
 TIME_BC_RECORD, TIME_BC_CTL, TIME_BC_HIST, TIME_BC_TABLE_MAX = 8, 4, 3, 1024
 TIME_BC_NONE, TIME_BC_CONST, TIME_BC_RAMP_LINEAR, TIME_BC_RAMP_SMOOTH, TIME_BC_SINE, TIME_BC_TABLE, TIME_BC_TABLE_PERIODIC = range(7)
+# GFV_TIME_SCHEME_* of include/gfv.h: words of the record, the schemes of gfv_time_scheme_update
+TIME_SCHEME_RECORD, TIME_SCHEME_BDF1, TIME_SCHEME_BDF2 = 4, 1, 2
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -228,6 +230,7 @@ _SIGNATURES = {
     "gfv_slice_softmax_token": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_slice_post_bwd": (C.c_int, [C.c_void_p] * 14 + [C.c_int32, C.c_int32, C.c_void_p]),
     "gfv_phi_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "gfv_phi_fwd_ts": (C.c_int, [C.c_void_p] * 6 + [C.c_int32, C.c_int32, C.c_void_p]),
     "gfv_phi_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
     "gfv_wlsq_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "gfv_wlsq_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
@@ -297,6 +300,7 @@ _SIGNATURES = {
     "gfv_field_stats_update": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_time_bc_update": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
                            + [C.c_int32] * 3 + [C.c_void_p]),
+    "gfv_time_scheme_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -52,6 +52,14 @@ steps find the level count they found before and write the same values again.  W
 (`gfv_time_bc`: one synchronisation) and `load_state_dict()` puts the boundary data of the level that comes next in place, so a
 march that resumes in a new object is driven as the uninterrupted one.  `time_bc=None` (the default) issues no new launch and
 allocates nothing.
+
+`time_scheme=TimeScheme("bdf2")` (gfv/timescheme.py): one more launch behind the march launch keeps the velocity of
+the last two levels in a ring and writes the baseline and the step of a second-order backward difference where the finite-volume
+section reads them - from the second level on (the first runs backward Euler, the usual start-up; `TimeScheme("bdf2", previous=)`
+starts at second order).  Second order in time needs `integrator="implicit"`.  Inner iterations and held steps find the level count
+they found before and write the same bits again.  With it `state_dict()` carries the previous level's velocity
+(`gfv_time_scheme`: one synchronisation) and `load_state_dict()` installs it, so a march that resumes in a new object on the
+carried-over field continues at second order.  `time_scheme=None` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -68,6 +76,7 @@ from . import timebc as TB
 from .fieldstats import FieldStats
 from .optstep import optimizer_launches
 from .schedule import Plateau
+from .timescheme import check_owner as check_time_scheme
 from .trainer import TrainStep
 
 # words of the march record (include/gfv.h gfv_march_advance)
@@ -145,7 +154,7 @@ def decode_history(words, B):
 
 class MarchStep(TrainStep):
     def __init__(self, model, graphs, *, max_inner=20, min_inner=1, tol=1e-2, abs_tol=None, max_levels=1000, keep=0,
-                 use_graph="list", field_stats=None, time_bc=None, **trainstep_kwargs):
+                 use_graph="list", field_stats=None, time_bc=None, time_scheme=None, **trainstep_kwargs):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
         if field_stats is not None and not isinstance(field_stats, FieldStats):
@@ -153,6 +162,7 @@ class MarchStep(TrainStep):
         if field_stats is not None:
             field_stats.check_free()
         TB.check_owner(time_bc, graphs)
+        check_time_scheme(time_scheme)
         self._march = None
         self.field_stats = None
         self.time_bc = None
@@ -179,6 +189,9 @@ class MarchStep(TrainStep):
         if time_bc is not None:
             # (its attach issues the launch for level 0's field: the level count is 0)
             self.time_bc = time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._march, LEVEL, self.max_levels)
+        if time_scheme is not None:
+            # (its attach issues the launch for level 0: the baseline of the initial field, second order with `previous=`)
+            self.time_scheme = time_scheme.attach(self, pl, self.x_backup, self._march, LEVEL)
 
     def __del__(self):
         host = getattr(self, "_mirror", None)
@@ -247,6 +260,12 @@ class MarchStep(TrainStep):
             self.hyper.data_ptr(), self._march.data_ptr(), self._r0.data_ptr(), self._hist.data_ptr(), self.max_levels,
             self._max_inner, self._min_inner, None if self._snap is None else self._snap.data_ptr(), self.keep, self._mirror_dev,
             L.stream_ptr()), "gfv_march_advance")
+        self._follow_level()
+
+    def _follow_level(self):
+        """The launches that follow the level count, behind the march launch.  They touch disjoint data (the statistics; the
+        boundary targets and the source column; the velocity ring and the time difference's two tensors) and none reads what
+        another writes: their order among themselves does not matter."""
         if self.field_stats is not None:
             # the clock is the level count: it moves on the launch that ends a level and on no other, so a level is sampled once,
             # whatever its inner count, and a held step samples nothing
@@ -255,6 +274,10 @@ class MarchStep(TrainStep):
             # the targets of level count + 1: new values behind the launch that ended a level, the same values again behind an inner
             # iteration or a held step (an early-out would need the blocks to agree on a "last" word: DESIGN.md 5u)
             self.time_bc.launch()
+        if self.time_scheme is not None:
+            # the ring's rotation and the next level's baseline behind the launch that ended a level; the same bits again behind an
+            # inner iteration or a held step.  It touches nothing the two launches above touch: their order does not matter
+            self.time_scheme.launch()
 
     def _adam(self):
         optimizer_launches(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper,
@@ -365,21 +388,34 @@ class MarchStep(TrainStep):
             self.field_stats.reset()
         if self.time_bc is not None:
             self.time_bc.reset()                      # (behind the record's zero: the data of level 0's field)
+        if self.time_scheme is not None:
+            self.time_scheme.reset()                  # (behind the record's zero: base = 0, level 0 is first order again)
 
     # ---- checkpoints -----------------------------------------------------------------------------------------------------------
     def state_dict(self):
         """TrainStep's; with `time_bc` also the time the boundary data have reached: `gfv_time_bc` = {"clock": levels completed,
-        this object's clock offset included} (one synchronisation).  The march record itself is not part of it."""
+        this object's clock offset included} (one synchronisation); with `time_scheme` also `gfv_time_scheme` = {"scheme",
+        "has_previous", "previous" [N, 2] CPU tensor}: the velocity of level count - 1 (one synchronisation).  The march record
+        itself is not part of it."""
         sd = super().state_dict()
+        if self.time_scheme is not None:
+            sd["gfv_time_scheme"] = self.time_scheme.state_dict()
         if self.time_bc is not None:
             sd["gfv_time_bc"] = {"clock": self._read_record()[LEVEL] + self.time_bc.clock_offset}
         return sd
 
     def load_state_dict(self, sd):
         """TrainStep's; with `time_bc` the boundary data of the level that comes next are put in place: clock = the saved count + 1
-        (a dict without `gfv_time_bc`: this object's own level count + 1).  The field itself is the caller's to carry over
-        (`graphs[0].x` of the new object, or `reset(x=)` before loading)."""
+        (a dict without `gfv_time_bc`: this object's own level count + 1); with `time_scheme` the saved previous level is
+        installed as the constructor's `previous=` would (a dict without `gfv_time_scheme`: the history is forgotten).  The field
+        itself is the caller's to carry over (`graphs[0].x` of the new object, or `reset(x=)` before loading)."""
+        saved_ts = sd.get("gfv_time_scheme") if self.time_scheme is not None else None
+        if saved_ts is not None and saved_ts.get("scheme") != self.time_scheme.scheme:
+            raise ValueError(f"the state of a {saved_ts.get('scheme')!r} time scheme does not load into a "
+                             f"{self.time_scheme.scheme!r} one")
         super().load_state_dict(sd)
+        if self.time_scheme is not None:
+            self.time_scheme.load_state_dict(saved_ts if saved_ts is not None else {"scheme": self.time_scheme.scheme})
         if self.time_bc is not None:
             saved = sd.get("gfv_time_bc")
             level = self._read_record()[LEVEL]

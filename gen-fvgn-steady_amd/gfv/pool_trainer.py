@@ -69,9 +69,13 @@ class PoolTrainStep(TrainStep):
     def __init__(self, model, pool, max_graphs=8, *, max_sizes=None, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None,
                  use_graph="list", max_list_bytes=16 << 30, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None,
+                 time_scheme=None):
         if use_graph not in (False, "list"):
             raise ValueError('PoolTrainStep: use_graph must be False or "list" (the hipGraph mode is bound to one batch)')
+        if time_scheme is not None:
+            raise ValueError("PoolTrainStep: time_scheme= is not supported (the pool owns the fields and keeps one level per entry: "
+                             "there is no previous level to difference against)")
         check_policy(max_grad_norm, skip_on_flag, bool(distributed))
         check_accum_steps(accum_steps, bool(distributed))
         check_ema(ema_decay, ema_warmup)

@@ -27,6 +27,7 @@ from .observe import Observations, check_observe
 from .optstep import optimizer_launches
 from .plan import _live_key, _refresh_live, get_plan
 from .schedule import check_schedule
+from .timescheme import check_owner as check_time_scheme
 from .trainlog import make_log
 
 
@@ -40,7 +41,8 @@ class TrainStep:
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
-                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None):
+                 decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None,
+                 time_scheme=None):
         # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
         # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
         dist_on = (world_size > 1) if distributed is None else bool(distributed)
@@ -51,6 +53,8 @@ class TrainStep:
         check_schedule(schedule)
         check_balance(balance, dist_on, world_size, type(self).__name__)
         check_observe(observations, balance, type(self).__name__, self._OBS_KIND)
+        check_time_scheme(time_scheme)
+        self.time_scheme = None
         self.schedule = None
         self.balance = None
         self.observations = None
@@ -145,6 +149,10 @@ class TrainStep:
         self.gloss = torch.zeros((B, 4), dtype=torch.float32, device=dev)
         self.losses = None
         self.uvp_node = None
+        # time differencing (gfv/timescheme.py): None - no launch, no allocation, the forward as it was.  Attached
+        # (last: nothing has been recorded yet), the finite-volume section reads its two tensors and advance_time() issues its launch
+        if time_scheme is not None:
+            self.time_scheme = time_scheme.attach(self, self.plan, self.x_backup)
 
     # hidden_size below 128 (FVMmodel/padding.py): parameters, moments and gradients of the TRUE shapes stay the state
     # (flat_p / flat_m / flat_v / flat_g, what Adam and the checkpoints see); every step gathers the parameters into the
@@ -601,6 +609,10 @@ class TrainStep:
             raise RuntimeError("advance_time() needs the prediction of a step (want_outputs=True)")
         self.x_backup[:, 0:3].copy_(self.uvp_node)
         self.x.copy_(self.x_backup)
+        if self.time_scheme is not None:
+            # the scheme's own clock word counts the fields written: bumped in stream order behind the two copies, then the launch
+            # that rotates the history and writes the next level's baseline where eager steps, lists and graphs read it
+            self.time_scheme.tick()
 
     def sync_from_model(self):
         """Call after loading a checkpoint into the model: `load_state_dict` copies into the parameter views of the flat
@@ -622,6 +634,8 @@ class TrainStep:
         if self.observations is not None:
             raise ValueError("set_batch() with observations attached: they belong to the nodes of ONE batch (changing batches are "
                              "PoolTrainStep's and gfv.observe.PoolObservations' job)")
+        if self.time_scheme is not None:
+            raise ValueError("set_batch() with a time scheme attached: its history belongs to the nodes of ONE batch")
         self.graphs = graphs
         self.plan = get_plan(graphs)
         self._live = _live_key(graphs)
@@ -644,7 +658,8 @@ class TrainStep:
             losses, uvp_node, uvp_cell, _, ctx = self.engine.forward(
                 self.P_run, self.model.node_norm.buffers_dict(), self.x, self.plan, norm_global=True, accumulate=accumulate,
                 want_outputs=self.want_outputs, want_edge_attr15=False, x_raw=self.x_backup,
-                train_loss=(self.hyper, self.loss, self.gloss))   # loss + its gradient behind the residual norms, same launch
+                train_loss=(self.hyper, self.loss, self.gloss),   # loss + its gradient behind the residual norms, same launch
+                time_state=None if self.time_scheme is None else self.time_scheme.time_state)
             obs, hook = self.observations, None
             if obs is not None:
                 # the data term (gfv/observe.py): loss and gloss re-formed with it behind the forward, its own gradient added to

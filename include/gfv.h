@@ -474,6 +474,11 @@ int gfv_slice_post_bwd(const float* xmid, const float* Ws, const float* bs, cons
  * ---------------------------------------------------------------------------------------------------------- */
 int gfv_phi_fwd(const float* dec, const float* y, const int32_t* node_type, const float* uv_old, float* phi, int32_t N,
                 int32_t mode, void* stream);
+/* gfv_phi_fwd with a separate baseline of the time difference (gfv_time_scheme_update): uv_hat is still formed from uv_old (u_n,
+ * what the input preparation wrote), channels 5 and 6 of phi carry uv_star.  gfv_phi_bwd is its adjoint too: the baseline carries
+ * no gradient. */
+int gfv_phi_fwd_ts(const float* dec, const float* y, const int32_t* node_type, const float* uv_old, const float* uv_star,
+                   float* phi, int32_t N, int32_t mode, void* stream);
 int gfv_phi_bwd(const float* gphi, const float* dec, const int32_t* node_type, float* gdec, int32_t N, int32_t mode,
                 void* stream);
 /* rowptr/outn/Bp: directed stencil in CSR order of the receiving node, Bp [S,5] permuted moment vectors;
@@ -1123,6 +1128,47 @@ int gfv_time_bc_update(const int32_t* clock, const int32_t* ctl, const double* r
                        const int32_t* batch, const int32_t* node_type, int32_t N, int32_t B, const float* y0, float* y,
                        const float* theta0, float* theta5, int32_t ld_theta, float* x_backup, float* x, double* hist,
                        int32_t K_max, int32_t type_mask, int32_t channels, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Time differencing of a march (gfv/timescheme.py): the history of a second-order backward difference (BDF2), kept
+ * on the device.  The momentum residual's time term is theta0 * (u - u_old) / dt * area and is linear in u_old, so BDF2 is that
+ * term with two substitutions: u_old -> u* = u_n + (u_n - u_{n-1}) / 3 and dt -> dt / 1.5, since
+ * (u - u*) / (dt / 1.5) = (3 u - 4 u_n + u_{n-1}) / (2 dt).  ONE launch behind whatever has advanced the field
+ * (gfv_march_advance, or the two copies of TrainStep.advance_time()), on the same stream, writes u* and the step the
+ * finite-volume section then reads (gfv_phi_fwd_ts; the `dt` of gfv_cell_fwd_ex, gfv_fvm_bwd_ex and gfv_fvm_mesh_t).
+ *   x_backup   [N, 12] float, 16-byte aligned: columns 0:2 of a row are the velocity (u, v), dimensional
+ *   batch      int32 [N]: the graph of a row;  uvp_dim  float [B, 3];  dt  float [B] (read, never written)
+ *   clock      the device address of one int32 counting the fields written so far: x_backup holds field *clock, field 0 is the
+ *              initial state (word [6] `level` of gfv_march_advance's record, or a word of the caller's own)
+ *   rec        GFV_TIME_SCHEME_RECORD int32 words, all written by the host only:
+ *     [0] scheme   GFV_TIME_SCHEME_BDF1 or GFV_TIME_SCHEME_BDF2
+ *     [1] base     the clock of the oldest field the ring is known to hold
+ *     [2], [3]     zero
+ *   ring       float [2, N, 2], 8-byte aligned: the velocity columns of the fields seen, one slot per clock parity
+ *   ustar      float [N, 2], 8-byte aligned: the dimensionless baseline of the time difference, in the form gfv_prep_apply's
+ *              uv_old has
+ *   dt_eff     float [B]: the step of the time difference
+ * The rule, with rec and *clock AS THE LAUNCH FINDS THEM (every thread reads them before anything is written; the launch
+ * writes neither):
+ *   c = *clock;  active = (scheme == GFV_TIME_SCHEME_BDF2) && (c > base)
+ *   row i < N of graph b = batch[i], channel k in {0, 1}:
+ *     cur = x_backup[i, k];  ring[c & 1][i][k] = cur
+ *     active:      prev = ring[(c & 1) ^ 1][i][k];  s = cur + (cur - prev) / 3.0f;  ustar[i][k] = s / uvp_dim[3 b + k]
+ *     otherwise:   ustar[i][k] = cur / uvp_dim[3 b + k]       (gfv_prep_apply's uv_old: the same operation, the same bits)
+ *   t < B:         dt_eff[t] = active ? dt[t] / 1.5f : dt[t]
+ * Every operation is ONE IEEE float operation in the order written, nothing contracted.  The launch reads only the ring slot it
+ * does not write, and x_backup: a launch that finds the same clock (an inner iteration, a held step of a march) writes the same
+ * bits again, and a launch that finds the clock advanced by one overwrites field c - 2 with field c and reads field c - 1 - the
+ * whole rotation.  One thread per row, no atomics, no sum across rows, no word written that another workgroup of the launch reads.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, N < 1, B < 1, an x_backup that is not 16-byte aligned or a ring / ustar that
+ * is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_TIME_SCHEME_RECORD 4
+#define GFV_TIME_SCHEME_BDF1 1
+#define GFV_TIME_SCHEME_BDF2 2
+int gfv_time_scheme_update(const float* x_backup, const int32_t* batch, const float* uvp_dim, const float* dt, int32_t N,
+                           int32_t B, const int32_t* clock, const int32_t* rec, float* ring, float* ustar, float* dt_eff,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
