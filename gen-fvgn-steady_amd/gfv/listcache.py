@@ -7,7 +7,8 @@ times, or whose list alone is larger than the budget, stays eager for good (it w
 recording allocates a whole step's activations afresh).
 
 `decide` / `store` / `invalidate` / `clear` are host code with no GPU in them; `run` is the step of the forward-only users
-(`Rollout`, `Sweep`, `Evaluate`) on top of them.  `PoolTrainStep` keeps its own step and calls the policy directly.
+(`Rollout`, `Sweep`, `Evaluate`) on top of them.  The training step (`TrainStep._issue`, shared by `PoolTrainStep` and `MarchStep`)
+has an all-reduce and the optimiser behind each path and a validity check in front, and calls the policy directly.
 """
 from __future__ import annotations
 
@@ -41,6 +42,9 @@ class ListCache(collections.abc.Mapping):
     # ---- the mapping view --------------------------------------------------------------------------------------------------
     def __getitem__(self, key):
         return self._entries[key]
+
+    def get(self, key, default=None):      # (the mixin's, in one dictionary look-up: it is on every step's path)
+        return self._entries.get(key, default)
 
     def __iter__(self):
         return iter(self._entries)

@@ -74,7 +74,6 @@ import torch
 from . import lib as L
 from . import timebc as TB
 from .fieldstats import FieldStats
-from .optstep import optimizer_launches
 from .schedule import Plateau
 from .timescheme import check_owner as check_time_scheme
 from .trainer import TrainStep
@@ -279,16 +278,8 @@ class MarchStep(TrainStep):
             # inner iteration or a held step.  It touches nothing the two launches above touch: their order does not matter
             self.time_scheme.launch()
 
-    def _adam(self):
-        optimizer_launches(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper,
-                           guard=self._guard, ema=self._ema, groups=self._pg, B=self.plan.B, loss=self.loss, hold=self._march)
-
-    def _log_step(self, entries=None, n_entries=0):
-        if self.log is None:
-            return
-        self.log.append(self.flat_g, self.flat_p, self.adam_state, self.hyper, self.loss, self.losses, self.plan.B,
-                        guard=self._guard.guard if self._guard.active else None, accum=self._march, entries=entries,
-                        n_entries=n_entries)
+    def _hold_record(self):
+        return self._march       # (word [3] = APPLY: the march launch of this step wrote it; the guard, Adam and the log read it)
 
     # ---- the run -------------------------------------------------------------------------------------------------------------
     def _read_record(self):

@@ -36,7 +36,11 @@ allocated and, for a batch larger than any before, re-allocated INSIDE a step by
 `TrainStep` over the same batches would do it (the padding slots of the flat gradient take whatever that workspace held, so its
 history is part of the bit-identity with the eager path) - and when that happens the new tensor is adopted and EVERY list is
 dropped (the old tensor dies with them; the keys keep their warm-up counts and record again on their next visit).  Before a
-replay the engine signature and the pointers of all five pieces are compared with what the list was recorded against; on any mismatch the list is dropped and the step runs eager.  A stale list is never issued.
+replay the engine signature and the pointers of all five pieces (`_list_stamp`) are compared with what the list was recorded
+against; on any mismatch the list is dropped and the step runs eager.  A stale list is never issued.
+
+The step itself is `TrainStep`'s (gfv/trainer.py: `_step_head`, `_issue`, `_step_tail`); what is the pool's lies between them:
+the load, the per-B `gloss`, the observations' gather, the scratch swap around `_issue`, and the payback.
 """
 from __future__ import annotations
 
@@ -44,18 +48,10 @@ import contextlib
 
 import torch
 
-from . import cmdlist
-from . import lib as L
 from . import listcache
-from .accum import check_accum_steps
-from .balance import check_balance
-from .ema import check_ema
-from .groups import check_groups
-from .guard import check_policy
-from .observe import PoolObservations, check_observe
-from .schedule import check_schedule
+from .observe import PoolObservations
 from .static_forward import prep_scratch
-from .trainer import TrainStep
+from .trainer import TrainStep, check_train_args
 from .trainlog import make_log
 
 _SCRATCH = ("_zero_e", "_dw_ws", "_dw_ws_main", "_prep_ws", "_fvm_cnt")
@@ -76,30 +72,21 @@ class PoolTrainStep(TrainStep):
         if time_scheme is not None:
             raise ValueError("PoolTrainStep: time_scheme= is not supported (the pool owns the fields and keeps one level per entry: "
                              "there is no previous level to difference against)")
-        check_policy(max_grad_norm, skip_on_flag, bool(distributed))
-        check_accum_steps(accum_steps, bool(distributed))
-        check_ema(ema_decay, ema_warmup)
-        check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
-        check_schedule(schedule)
-        check_balance(balance, bool(distributed), 1, "PoolTrainStep")
-        check_observe(observations, balance, "PoolTrainStep", PoolObservations)
+        step_kw = dict(lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, want_outputs=want_outputs, distributed=distributed,
+                       max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
+                       ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay, param_groups=param_groups,
+                       decoupled_weight_decay=decoupled_weight_decay, schedule=schedule, balance=balance, observations=observations)
+        check_train_args("PoolTrainStep", PoolObservations, model, **step_kw)      # (TrainStep's, before the arena is allocated)
         if observations is not None and observations.pool is not pool:
             raise ValueError("PoolTrainStep: the PoolObservations were built on another pool than the one to train on")
         self.pool = pool
         self.arena = pool.arena(max_graphs, max_sizes)
-        self.max_list_bytes = int(max_list_bytes)
+        self.max_list_bytes = int(max_list_bytes)                   # (TrainStep builds `_lists` with it: key -> Entry with scratch)
         log = make_log(log, self.arena.max_graphs)                  # (before anything is built: its arguments are checked here)
         graphs, _ = self.arena.load([0])
-        super().__init__(model, graphs, lr=lr, betas=betas, eps=eps, loss_weights=loss_weights, world_size=1, use_graph=use_graph,
-                         want_outputs=want_outputs, distributed=distributed, max_grad_norm=max_grad_norm,
-                         skip_nonfinite=skip_nonfinite, skip_on_flag=skip_on_flag, accum_steps=accum_steps,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
-                         decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, log=log,
-                         schedule=schedule, balance=balance, observations=observations)
+        super().__init__(model, graphs, use_graph=use_graph, log=log, **step_kw)
         self.x_backup = graphs[0]._gfv_x_raw                      # the arena's raw state, not a per-batch clone
         self._gloss = {self.plan.B: self.gloss}                     # one per batch size, kept: recorded lists point at them
-        self._graphs = listcache.ListCache(self.max_list_bytes)     # key -> Entry with engine_sig, early, scratch
-        self._list_warm = self._graphs.warm                         # (TrainStep._drop_recorded clears both)
         dev, cap = self.dev, self.arena.capacity
         self._zero_e_cap = torch.zeros((max(cap["e"], 1), 128), dtype=torch.float32, device=dev)
         self._zero_views = {}
@@ -107,9 +94,6 @@ class PoolTrainStep(TrainStep):
         self._scratch = dict(_zero_e=None, _dw_ws=None, _dw_ws_main=None, _prep_ws=prep_ws, _fvm_cnt=fvm_cnt)
 
     # ---- bookkeeping ---------------------------------------------------------------------------------------------------
-    def stats(self):
-        return self._graphs.stats()
-
     def set_batch(self, graphs):
         raise TypeError("PoolTrainStep takes its batch per step: step(indices)")
 
@@ -143,10 +127,13 @@ class PoolTrainStep(TrainStep):
             if grown[0]:
                 # ... and no list recorded against the old one survives.  The warm-up counts stay: what a key needs of the
                 # workspace depends on its sizes alone, and the new one is at least as large
-                self._graphs.clear(keep_warm=True)
+                self._lists.clear(keep_warm=True)
 
-    def _valid(self, ent):
-        return ent.engine_sig == self.engine.capture_signature() and ent.scratch == self._scratch_ptrs()
+    def _list_stamp(self):
+        return dict(super()._list_stamp(), scratch=self._scratch_ptrs())      # (the engine works on this object's scratch now)
+
+    def _list_valid(self, ent):
+        return super()._list_valid(ent) and ent.scratch == self._scratch_ptrs()
 
     # ---- one step ------------------------------------------------------------------------------------------------------
     def step(self, indices, payback=False, advance=False):
@@ -156,9 +143,7 @@ class PoolTrainStep(TrainStep):
         loss and entries, the reduced gradient).
         payback: write the predicted (u, v, p) back into the entries' own `x` (one launch); advance: also into the arena's raw
         state, so that the next inner step over the SAME batch starts from it (`TrainStep.advance_time`)."""
-        self._not_swapped("step()")
-        self._check_aliasing()
-        L.raise_on_status("PoolTrainStep.step")
+        self._step_head("PoolTrainStep.step")
         idx = [int(i) for i in indices]
         graphs, plan = self.arena.load(idx)
         sig = self.arena._last[1]
@@ -173,44 +158,13 @@ class PoolTrainStep(TrainStep):
             # the step in every launch mode - the recorded body reads the buffers, never the entries
             self.observations.gather(idx, plan)
         acc = self.model.node_norm.should_accumulate()
-        dist_on = self.dist_on
-        key = (sig, acc, dist_on)
-        listed = self.use_graph == "list" and not (acc and dist_on)
-        recorded = None
+        key = (sig, acc, self.dist_on)
         with self._own_scratch(plan.E) as grown:
-            ent = self._graphs.get(key)
-            if ent is not None and not self._valid(ent):
-                # something a recorded launch points at moved (weight-image set, product form, a piece of scratch): the list is
-                # dropped and this step runs eager - a stale list is never issued
-                self._graphs.invalidate(key)
-            what = self._graphs.decide(key, listed)
-            if what == "replay":
-                ent.cl.replay()
-                self.losses, self.uvp_node, self.uvp_cell = ent.outs
-                if dist_on:
-                    self._allreduce(ent.early)
-                    self._adam()
-            elif what == "eager":
-                self._eager(acc, dist_on)
-            else:
-                before = torch.cuda.memory_reserved(self.dev)
-                with cmdlist.record() as cl:
-                    early = self._hooked_body(acc, dist_on)
-                nbytes = max(torch.cuda.memory_reserved(self.dev) - before, 0)   # the segments of the list's private pool
-                if dist_on:
-                    self._allreduce(early)
-                    self._adam()
-                recorded = (cl, early, nbytes)
-        if recorded is not None and not grown[0]:    # (a workspace that moved while the list was recorded: the list is not kept)
-            cl, early, nbytes = recorded
-            self._graphs.store(key, listcache.Entry(cl, nbytes, (self.losses, self.uvp_node, self.uvp_cell), early=early,
-                                                    engine_sig=self.engine.capture_signature(), scratch=self._scratch_ptrs()))
-        if acc:
-            self.model.node_norm.note_accumulated()
-        if self._accum is not None:
-            self._accum.note_step()
-        self._log_step(idx, self.pool.n)     # (eager, behind Adam, outside the list: the row carries this step's entries)
-        self._balance_step()                 # (eager, outside the list too: losses differs per list, B per batch)
+            ent = self._issue(key, acc, self.dist_on, self._listed(acc))
+        if ent is not None and not grown[0]:         # (a workspace that moved while the list was recorded: the list is not kept)
+            self._lists.store(key, ent)
+        # (the log and the balancer: eager, behind Adam, outside the list - the row carries this step's entries, B differs per batch)
+        self._step_tail(acc, idx, self.pool.n)
         if payback or advance:
             if self.uvp_node is None:
                 raise RuntimeError("payback needs the prediction of the step (want_outputs=True)")

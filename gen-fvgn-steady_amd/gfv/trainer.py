@@ -5,17 +5,22 @@ Reproduces the call sequence of the reference's drivers for ONE batch kept on th
 pre_train_Adam.py:158-191: zero_grad, forward, `mean(log(weighted residuals))`, backward, Adam), without the autograd
 tape: parameters, gradients and Adam moments live in flat fp32 buffers, so the optimiser is one kernel and the
 data-parallel exchange is ONE all-reduce of 4.7 MB.  The fixed launch sequence can be captured into
-a hipGraph (torch.cuda.CUDAGraph) to remove host launch overhead.
+a hipGraph (torch.cuda.CUDAGraph, kept in `_captures`) or recorded as a command list (gfv/cmdlist.py, kept in `_lists`: a
+`gfv.listcache.ListCache`, the policy of every recorded path) to remove host launch overhead.
+
+One step skeleton serves `TrainStep`, `gfv.pool_trainer.PoolTrainStep` and `gfv.march.MarchStep`: `_step_head`, a launch path (`_issue`:
+eager, recorded or replayed; `_capture_step`: hipGraph), `_step_tail`.  A subclass adds through hooks: `_after_backward` (launches in
+the body), `_hold_record` (whose apply flag the optimiser reads), `_list_stamp` / `_list_valid` (what a list must find unmoved).
 """
 from __future__ import annotations
 
 import contextlib
-import os
 
 import torch
 
 from . import cmdlist
 from . import lib as L
+from . import listcache
 from .accum import GradAccum, check_accum_steps
 from .balance import check_balance
 from .ema import WeightEMA, check_ema
@@ -35,25 +40,40 @@ def _gather(src, index, out):
     torch.index_select(src, 0, index, out=out)
 
 
+def check_train_args(who, obs_kind, model, *, world_size=1, distributed=None, max_grad_norm=None, skip_on_flag=False,
+                     accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0, decoupled_weight_decay=True,
+                     param_groups=None, schedule=None, balance=None, observations=None, time_scheme=None, **unchecked):
+    """The constructor checks of the step objects, in the order they have always been made; needs no GPU.  who: the class name the
+    messages carry; obs_kind: what its `observations=` takes; the keywords are TrainStep's (`unchecked`: those nothing is checked
+    of).  -> (dist_on, accum_steps, ema_decay, the GroupSpec)"""
+    # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
+    # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
+    dist_on = (world_size > 1) if distributed is None else bool(distributed)
+    check_policy(max_grad_norm, skip_on_flag, dist_on)
+    accum_steps = check_accum_steps(accum_steps, dist_on)
+    ema_decay = check_ema(ema_decay, ema_warmup)
+    spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
+    check_schedule(schedule)
+    check_balance(balance, dist_on, world_size, who)
+    check_observe(observations, balance, who, obs_kind)
+    check_time_scheme(time_scheme)
+    return dist_on, accum_steps, ema_decay, spec
+
+
 class TrainStep:
     _OBS_KIND = Observations          # what `observations=` takes (PoolTrainStep: PoolObservations)
+    max_list_bytes = None             # the byte budget of the recorded lists: unbounded (PoolTrainStep: its argument)
 
     def __init__(self, model, graphs, *, lr=None, betas=(0.9, 0.999), eps=1e-8, loss_weights=None, world_size=1,
                  process_group=None, use_graph=False, want_outputs=True, distributed=None, max_grad_norm=None,
                  skip_nonfinite=False, skip_on_flag=False, accum_steps=1, ema_decay=None, ema_warmup=True, weight_decay=0.0,
                  decoupled_weight_decay=True, param_groups=None, log=None, schedule=None, balance=None, observations=None,
                  time_scheme=None):
-        # distributed=True with world_size 1 sends the step through the same collectives (identity all-reduce): the
-        # RCCL path can then be exercised on a single GPU (tests/test_rccl_gpu.py)
-        dist_on = (world_size > 1) if distributed is None else bool(distributed)
-        check_policy(max_grad_norm, skip_on_flag, dist_on)
-        accum_steps = check_accum_steps(accum_steps, dist_on)
-        ema_decay = check_ema(ema_decay, ema_warmup)
-        spec = check_groups(*model.param_names_tensors(), weight_decay, decoupled_weight_decay, param_groups)
-        check_schedule(schedule)
-        check_balance(balance, dist_on, world_size, type(self).__name__)
-        check_observe(observations, balance, type(self).__name__, self._OBS_KIND)
-        check_time_scheme(time_scheme)
+        dist_on, accum_steps, ema_decay, spec = check_train_args(
+            type(self).__name__, self._OBS_KIND, model, world_size=world_size, distributed=distributed, max_grad_norm=max_grad_norm,
+            skip_on_flag=skip_on_flag, accum_steps=accum_steps, ema_decay=ema_decay, ema_warmup=ema_warmup, weight_decay=weight_decay,
+            decoupled_weight_decay=decoupled_weight_decay, param_groups=param_groups, schedule=schedule, balance=balance,
+            observations=observations, time_scheme=time_scheme)
         self.time_scheme = None
         self.schedule = None
         self.balance = None
@@ -115,8 +135,11 @@ class TrainStep:
         # averaged weights (gfv/ema.py): None with ema_decay None - no third buffer, _adam() as it was
         self._ema_warmup = bool(ema_warmup)
         self._ema = WeightEMA(self.flat_p, total, ema_decay, self._ema_warmup) if ema_decay is not None else None
+        # what has been recorded of the step: command lists per (accumulate, distributed) under the one list policy (gfv/listcache.py:
+        # warm up, record once, replay, never issue a stale list); hipGraph captures as (CUDAGraph, engine signature) per the same key
+        self._lists = listcache.ListCache(self.max_list_bytes, dev=dev)
+        self._captures = {}
         # parameter groups (gfv/groups.py): None with everything at its default - no table, _adam() as it was
-        self._graphs, self._list_warm = {}, {}
         self.log = None
         spec.skip = set(self.G.skip)
         spec.check_some_live([g["frozen"] for g in spec.groups])
@@ -254,9 +277,15 @@ class TrainStep:
     skip_on_flag = property(lambda self: self._guard.skip_on_flag)
 
     def _drop_recorded(self):
-        """Recorded lists and captured graphs hold the launch sequence and the addresses of the moment they were made."""
-        self._graphs.clear()
-        self._list_warm.clear()
+        """Recorded lists and captured graphs hold the launch sequence and the addresses of the moment they were made.  Every key
+        warms up again before it is recorded again."""
+        self._lists.clear()
+        self._captures.clear()
+
+    def stats(self):
+        """{"replayed", "recorded", "eager", "lists", "list_bytes"}: steps per path of `_issue` (a hipGraph step counts nowhere),
+        lists kept, the bytes of their private pools.  Host counts: no synchronisation."""
+        return self._lists.stats()
 
     def _set_guard(self, **kw):
         g = self._guard
@@ -643,8 +672,7 @@ class TrainStep:
         self.x_backup = self.x.clone()
         if self.gloss.shape[0] != self.plan.B:
             self.gloss = torch.zeros((self.plan.B, 4), dtype=torch.float32, device=self.dev)
-        self._graphs = {}
-        self._list_warm = {}
+        self._drop_recorded()
 
     # one un-captured step body ------------------------------------------------------------------------------
     def _body(self, accumulate, with_adam=True):
@@ -679,10 +707,16 @@ class TrainStep:
         """Launches of a subclass between the backward and the optimiser's (gfv.march.MarchStep: the march launch): part of the
         step body, so eager steps, recorded lists and captures carry them alike.  Nothing here."""
 
+    def _hold_record(self):
+        """A device record whose word [3] a launch of `_after_backward` wrote as this step's apply flag (`hold=` of gfv/optstep.py),
+        or None.  The optimiser and the log read it where they read the accumulation's record: an owner has one or the other."""
+        return None
+
     def _adam(self):
         """The optimiser step's one to three launches (gfv/optstep.py): eager, list and hipGraph mode all go through here."""
         optimizer_launches(self.flat_p, self.flat_g, self.flat_m, self.flat_v, self.n_params, self.adam_state, self.hyper,
-                           guard=self._guard, accum=self._accum, ema=self._ema, groups=self._pg, B=self.plan.B, loss=self.loss)
+                           guard=self._guard, accum=self._accum, ema=self._ema, groups=self._pg, B=self.plan.B, loss=self.loss,
+                           hold=self._hold_record())
 
     # data-parallel exchange: the flat gradient is reduced in two buckets.  The upper one (last processor + decoder:
     # their backward runs first) goes out on a communication stream as soon as its last gradient kernel is launched and
@@ -741,11 +775,43 @@ class TrainStep:
             self.engine.bucket_hook = None
         return self._early
 
-    def _eager(self, acc, dist_on):
-        self._hooked_body(acc, dist_on)
+    def _list_stamp(self):
+        """What a recorded list points at and does not own, as it is now: kept in the list's entry when it is recorded and compared
+        before every replay.  Here the engine's weight-image set and product form."""
+        return {"engine_sig": self.engine.capture_signature()}
+
+    def _list_valid(self, ent):
+        """Whether everything `_list_stamp` named when the list of `ent` was recorded is still where it was."""
+        return ent.engine_sig == self.engine.capture_signature()
+
+    def _issue(self, key, acc, dist_on, listed):
+        """The step body on the launch path of `key` (gfv/listcache.py): replayed from its list, eager (not `listed`, or a warm-up:
+        the first steps settle the weight-image set and the persistent workspaces), or recorded - the eager launch sequence taken
+        down at the C ABI and replayed with one ctypes call per launch: same two streams, same event edges, no per-launch Python
+        work.  A list that finds something it points at moved is dropped, and the step is the first of a new warm-up: a stale list
+        is never issued.  Under `dist_on` the rest of the exchange and the optimiser follow on every path, outside the list (the
+        early bucket's fork + all-reduce are inside).  -> the Entry of a list recorded just now, for the caller to store, or None."""
+        ent = self._lists.get(key)
+        if ent is not None and not self._list_valid(ent):
+            self._lists.invalidate(key)
+        what = self._lists.decide(key, listed)
+        new = None
+        if what == "replay":
+            ent.cl.replay()
+            self.losses, self.uvp_node, self.uvp_cell = ent.outs      # (the recorded step's own tensors: every replay rewrites them)
+            early = ent.early
+        elif what == "eager":
+            early = self._hooked_body(acc, dist_on)
+        else:
+            before = torch.cuda.memory_reserved(self.dev)
+            with cmdlist.record() as cl:
+                early = self._hooked_body(acc, dist_on)
+            nbytes = max(torch.cuda.memory_reserved(self.dev) - before, 0)   # the segments of the list's private pool
+            new = listcache.Entry(cl, nbytes, (self.losses, self.uvp_node, self.uvp_cell), early=early, **self._list_stamp())
         if dist_on:
-            self._allreduce()
+            self._allreduce(early)
             self._adam()
+        return new
 
     def _log_step(self, entries=None, n_entries=0):
         """The training log's two launches (gfv/trainlog.py), eagerly on the current stream behind the optimiser launches of the
@@ -756,7 +822,8 @@ class TrainStep:
             return
         self.log.append(self.flat_g, self.flat_p, self.adam_state, self.hyper, self.loss, self.losses, self.plan.B,
                         guard=self._guard.guard if self._guard.active else None,
-                        accum=None if self._accum is None else self._accum.rec, entries=entries, n_entries=n_entries)
+                        accum=self._hold_record() if self._accum is None else self._accum.rec, entries=entries,
+                        n_entries=n_entries)
 
     def _balance_step(self):
         """The balancer's launch (gfv/balance.py), eagerly on the current stream behind the optimiser launches of the step and
@@ -779,99 +846,89 @@ class TrainStep:
                 self._drop_recorded()
                 return
 
+    def _step_head(self, who):
+        """What every step does first.  who: the name the status error carries."""
+        self._not_swapped("step()")
+        self._check_aliasing()
+        # what the kernels of the steps BEFORE the last one raised in the device status word (a hidden activation outside the
+        # fixed-scale fp16 window, a weight-gradient operand beyond fp16): read from the pinned mirror the fused Adam publishes
+        # into - no synchronisation; the step that overflowed has long finished when its successor is issued
+        L.raise_on_status(who)
+        # caller-owned data the plan holds copies of (Dirichlet targets, node / face types, theta_PDE, sigma, uvp_dim, dt_graph):
+        # an in-place edit between two steps reaches the plan's tensors here - copied in place, so the pointers a captured step
+        # holds stay valid (the reference re-reads graph_node.y / graph_Index on every forward, importer.py:141-154,168).
+        # Batches of a DevicePool carry their plan with them: nothing to refresh.
+        live = _live_key(self.graphs)
+        if live != self._live:
+            _refresh_live(self.plan, self.graphs)
+            self._live = live
+
+    def _step_tail(self, acc, entries=None, n_entries=0):
+        """What every step does last, behind the optimiser's launches however they were issued -> the (device) loss."""
+        if acc:
+            self.model.node_norm.note_accumulated()
+        if self._accum is not None:
+            self._accum.note_step()
+        self._log_step(entries, n_entries)
+        self._balance_step()
+        return self.loss
+
+    def _listed(self, acc):
+        """Whether this step goes through its recorded list.  (An accumulating data-parallel step exchanges the Normalizer
+        statistics inside the forward: neither recorded nor captured.)"""
+        return self.use_graph == "list" and not (acc and self.dist_on)
+
     def step(self):
         """One training iteration.  Returns the (device) scalar loss tensor of this rank's batch.
         `use_graph`: False = eager launches, True = hipGraph replay, "list" = command-list replay.
         With `log=...` the step also appends one row to `self.log` (gfv/trainlog.py): read it with `ts.log.read()` when
         convenient - nothing in step() waits for the device.  Under data parallelism the log is rank-local (this rank's loss,
         the reduced gradient)."""
-        self._not_swapped("step()")
-        self._check_aliasing()
-        # what the kernels of the steps BEFORE the last one raised in the device status word (a hidden activation outside the
-        # fixed-scale fp16 window, a weight-gradient operand beyond fp16): read from the pinned mirror the fused Adam publishes
-        # into - no synchronisation; the step that overflowed has long finished when its successor is issued
-        L.raise_on_status("TrainStep.step")
-        # caller-owned data the plan holds copies of (Dirichlet targets, node / face types, theta_PDE, sigma, uvp_dim, dt_graph):
-        # an in-place edit between two steps reaches the plan's tensors here - copied in place, so the pointers a captured step
-        # holds stay valid (the reference re-reads graph_node.y / graph_Index on every forward, importer.py:141-154,168).
-        # Batches of a DevicePool carry their plan with them and are refreshed the same way.
-        live = _live_key(self.graphs)
-        if live != self._live:
-            _refresh_live(self.plan, self.graphs)
-            self._live = live
+        self._step_head("TrainStep.step")
         acc = self.model.node_norm.should_accumulate()
         dist_on = self.dist_on
-        if not self.use_graph or (acc and dist_on):
-            # (an accumulating data-parallel step exchanges the Normalizer statistics inside the forward: not captured)
-            self._eager(acc, dist_on)
-        elif self.use_graph == "list":
-            # command-list replay (gfv/cmdlist.py): the eager launch sequence of one step, recorded at the C ABI and
-            # replayed with one ctypes call per launch - same two streams, same event edges, no per-launch Python work
-            key = ("list", acc, dist_on)
-            entry = self._graphs.get(key)
-            sig = self.engine.capture_signature()
-            if entry is not None and entry[1] != sig:
-                self._graphs.pop(key)
-                self._list_warm.pop(key, None)
-                entry = None
-            if entry is None:
-                warm = self._list_warm.get(key, 0)
-                if warm < 2:
-                    # the first steps settle the weight-image set and the persistent workspaces (allocated outside the pool)
-                    self._list_warm[key] = warm + 1
-                    self._eager(acc, dist_on)
-                else:
-                    with cmdlist.record() as cl:
-                        early = self._hooked_body(acc, dist_on)   # (the early bucket's fork + all-reduce are part of the list)
-                    self._graphs[key] = (cl, self.engine.capture_signature(), early)
-                    if dist_on:
-                        self._allreduce(early)
-                        self._adam()
-            else:
-                entry[0].replay()
-                if dist_on:
-                    self._allreduce(entry[2])
-                    self._adam()
+        key = (acc, dist_on)
+        if self.use_graph and self.use_graph != "list" and not (acc and dist_on):
+            self._capture_step(key, acc, dist_on)
         else:
-            key = (acc, dist_on)
-            g = self._graphs.get(key)
-            if g is not None and g[1] != self.engine.capture_signature():
-                # the captured launches hold raw pointers into the weight-image set / descriptor tables of the engine:
-                # a changed set (model.to(), re-flattened parameters, a new weight block) makes every capture stale
-                self._drop_recorded()   # (command lists too: they re-record only after new warm-up steps)
-                g = None
-            if g is None:
-                # warm the allocator on a side stream, then capture (PyTorch CUDA-graph recipe)
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._snapshot()
-                    # twice: the first pass notes the weight blocks of the chain launches, the second allocates and
-                    # builds their split-fp16 images - the capture then records the launch sequence of a steady step
-                    for _ in range(2 if self.engine.f16split else 1):
-                        self._body(acc, with_adam=not dist_on)
-                        self._restore()
-                torch.cuda.current_stream().wait_stream(s)
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                # (thread_local: the RCCL watchdog thread of a process group polls events while this thread captures; under
-                # the default global mode that poll invalidates the capture and aborts the process)
-                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            ent = self._issue(key, acc, dist_on, self._listed(acc))
+            if ent is not None:
+                self._lists.store(key, ent)
+        return self._step_tail(acc)
+
+    def _capture_step(self, key, acc, dist_on):
+        """The step as a hipGraph replay; captured on the first visit of `key` and after the engine's signature moved."""
+        g = self._captures.get(key)
+        if g is not None and g[1] != self.engine.capture_signature():
+            # the captured launches hold raw pointers into the weight-image set / descriptor tables of the engine:
+            # a changed set (model.to(), re-flattened parameters, a new weight block) makes every capture stale
+            self._drop_recorded()   # (command lists too: they re-record only after new warm-up steps)
+            g = None
+        if g is None:
+            # warm the allocator on a side stream, then capture (PyTorch CUDA-graph recipe)
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                self._snapshot()
+                # twice: the first pass notes the weight blocks of the chain launches, the second allocates and
+                # builds their split-fp16 images - the capture then records the launch sequence of a steady step
+                for _ in range(2 if self.engine.f16split else 1):
                     self._body(acc, with_adam=not dist_on)
-                g = (g, self.engine.capture_signature())
-                self._graphs[key] = g
-                self._restore()  # capture does not execute; state is as before this step
-            g[0].replay()
-            if dist_on:
-                self._allreduce()
-                self._adam()
-        if acc:
-            self.model.node_norm.note_accumulated()
-        if self._accum is not None:
-            self._accum.note_step()
-        self._log_step()
-        self._balance_step()
-        return self.loss
+                    self._restore()
+            torch.cuda.current_stream().wait_stream(s)
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            # (thread_local: the RCCL watchdog thread of a process group polls events while this thread captures; under
+            # the default global mode that poll invalidates the capture and aborts the process)
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._body(acc, with_adam=not dist_on)
+            g = (g, self.engine.capture_signature())
+            self._captures[key] = g
+            self._restore()  # capture does not execute; state is as before this step
+        g[0].replay()
+        if dist_on:
+            self._allreduce()
+            self._adam()
 
     # state snapshot so the capture warm-up does not advance training ---------------------------------------
     def _state_tensors(self):
@@ -882,8 +939,8 @@ class TrainStep:
                 + (() if self._ema is None else (self._ema.e, self._ema.rec)))
 
     def _snapshot(self):
-        self._snap = tuple(t.clone() for t in self._state_tensors())
+        self._capture_state = tuple(t.clone() for t in self._state_tensors())
 
     def _restore(self):
-        for dst, src in zip(self._state_tensors(), self._snap):
+        for dst, src in zip(self._state_tensors(), self._capture_state):
             dst.copy_(src)

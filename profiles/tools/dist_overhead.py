@@ -29,7 +29,7 @@ for distributed in (False, True):
     print(f"distributed={distributed}: {1e3 * t_all / n:.3f} ms/step, host issue {1e3 * t_issue / n:.3f} ms/step")
     if distributed:
         # pieces, host side
-        cl = next(v for k, v in ts._graphs.items() if k[0] == "list")[0]
+        cl = next(iter(ts._lists.values())).cl
         hs = {"replay": 0.0, "allreduce": 0.0, "adam": 0.0}
         torch.cuda.synchronize()
         for _ in range(n):

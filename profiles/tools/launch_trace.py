@@ -137,7 +137,7 @@ def main():
     for step in range(6):
         print(f"# step {step}")
         ts.step()
-        cl = next((v[0] for k, v in ts._graphs.items() if isinstance(k, tuple) and k[0] == "list"), None)
+        cl = next((e.cl for e in ts._lists.values()), None)
         if cl is not None:
             break
     torch.cuda.synchronize()

@@ -73,7 +73,7 @@ def main():
            "ms_per_step": {}, "recorded_commands": {}}
     for name, v in times.items():
         out["ms_per_step"][name] = {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
-        out["recorded_commands"][name] = sorted(len(e[0]) for e in legs[name]._graphs.values())
+        out["recorded_commands"][name] = sorted(len(e.cl) for e in legs[name]._lists.values())
     out["observed_minus_plain_us"] = round(1e3 * (out["ms_per_step"]["observed"]["median"]
                                                   - out["ms_per_step"]["plain"]["median"]), 2)
 

@@ -70,7 +70,8 @@ def main():
     split = ts._bucket_split()
     assert 0 < split < ts.flat_g.numel() and ts._comm is not None and not ts._early, (split, ts._comm, ts._early)
     if mode == "list":
-        (cl, _, early), = ts._graphs.values()
+        (ent,) = ts._lists.values()
+        cl, early = ent.cl, ent.early
         assert early and sum(1 for c in cl.cmds if c[2] is not None and c[2] == ts._comm) == 1, "the early bucket is not part of the command list"
     mine = torch.cat([ts.P[k].reshape(-1) for k in ts.P] + [model.node_norm.acc_sum.reshape(-1),
                                                           model.node_norm.acc_sum_squared.reshape(-1),

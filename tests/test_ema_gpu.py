@@ -295,7 +295,7 @@ def test_trainstep_modes_agree_and_adam_is_the_plain_step(frozen_sd, eager_ema, 
     assert abs(st["w"] - ema_weight(float(np.float32(0.9)), True, 6)) <= 2.0 ** -22
     assert plain.ema_stats()["updates"] == 0 and plain.ema_stats()["decay"] is None
     if mode == "list":
-        assert any(isinstance(k, tuple) and k[0] == "list" for k in ts._graphs)
+        assert len(ts._lists) >= 1
     # the average is one: not the iterate, and between the start and the iterate where the parameters moved one way
     e, p = _ema_bits(ts)[0], _named_bits(ts)[0]
     assert not torch.equal(e, p)
@@ -339,20 +339,20 @@ def test_trainstep_a_skipped_step_is_not_averaged(frozen_sd):
 def test_attributes_follow_without_a_new_launch_sequence(frozen_sd):
     from gfv.ema import ema_weight
     ts = _run(frozen_sd, "list", ema_decay=0.9)
-    lists = dict(ts._graphs)
+    lists = dict(ts._lists)
     assert lists
     ts.ema_decay = 0.5                            # a value: through gfv_ema_init, the count stays, the lists stay
     st = ts.ema_stats()
     assert st["decay"] == 0.5 and st["updates"] == 6 and st["w"] == pytest.approx(ema_weight(0.5, True, 6), abs=2.0 ** -22)
     ts.ema_warmup = False
     st = ts.ema_stats()
-    assert st["warmup"] is False and st["updates"] == 6 and st["w"] == 0.5 and dict(ts._graphs) == lists
+    assert st["warmup"] is False and st["updates"] == 6 and st["w"] == 0.5 and dict(ts._lists) == lists
     ts.step()
     assert ts.ema_stats()["updates"] == 7
     with pytest.raises(ValueError, match="ema_decay"):
         ts.ema_decay = 1.0
     ts.ema_decay = None                           # off: the launch sequence changes, the lists go
-    assert ts._ema is None and not ts._graphs
+    assert ts._ema is None and not ts._lists and not ts._captures
     with pytest.raises(RuntimeError, match="ema_decay"):
         ts.ema_parameters()
     ts.ema_decay = 0.9                            # ... and on again: from the current parameters, counted from zero

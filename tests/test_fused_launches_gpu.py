@@ -156,7 +156,7 @@ def test_recorded_step_with_delayed_side_bursts_is_bit_identical(monkeypatch):
         for _ in range(8):
             ts.step()
         torch.cuda.synchronize()
-        cl = ts._graphs[("list", False, False)][0] if ("list", False, False) in ts._graphs else next(iter(ts._graphs.values()))[0]
+        cl = (ts._lists[(False, False)] if (False, False) in ts._lists else next(iter(ts._lists.values()))).cl
         res[delay] = ([ts.loss.clone(), ts.losses.clone(), ts.uvp_node.clone(), ts.flat_p.clone(), ts.flat_m.clone(), ts.flat_v.clone()],
                       getattr(cl, "delayed", 0))
     from gfv import cmdlist

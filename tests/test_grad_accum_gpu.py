@@ -316,7 +316,7 @@ def test_trainstep_two_micro_steps_of_one_batch_are_one_plain_step(frozen_sd, mo
     assert st["micro"] == 0 and st["graphs"] == 0 and st["closed"] == m      # (a hipGraph warm-up counts nothing)
     assert st["loss_mean"] == float(ts.loss)                                  # (2 l + 2 l) / 4
     if mode == "list":
-        assert any(isinstance(k, tuple) and k[0] == "list" for k in ts._graphs)
+        assert len(ts._lists) >= 1
     assert set(ts.state_dict()) == set(plain.state_dict())                   # an open accumulation is not state
 
 

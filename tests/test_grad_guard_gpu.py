@@ -299,7 +299,7 @@ def test_trainstep_with_an_idle_guard_is_bit_identical_in_every_mode(mode):
     assert st["clipped"] == st["skipped_nonfinite"] == st["skipped_flag"] == 0      # (a hipGraph warm-up counts nothing)
     assert float(out[True][2].adam_state[0]) == 5.0
     if mode == "list":
-        assert any(isinstance(k, tuple) and k[0] == "list" for k in out[True][2]._graphs)
+        assert len(out[True][2]._lists) >= 1
     # the guard's counters are not optimizer state: torch.optim.Adam loads the state_dict as before
     model2, _ = _model()
     opt = torch.optim.Adam(model2.parameters(), lr=LR)
@@ -322,7 +322,7 @@ def test_clipped_count_is_the_number_of_steps_above_the_bound():
         above += int(hit)
         assert (st["coef"] < 1.0) == hit and st["decision"] == (CLIP if hit else 0)
     assert above >= 1 and ts.guard_stats()["clipped"] == above
-    assert any(isinstance(k, tuple) and k[0] == "list" for k in ts._graphs)
+    assert len(ts._lists) >= 1
     with pytest.raises(ValueError):
         ts.max_grad_norm = -1.0
 

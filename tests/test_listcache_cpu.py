@@ -158,6 +158,32 @@ def test_unbounded_never_evicts_and_never_marks_a_key_oversize():
     _stats(c, replayed=20, recorded=20, eager=40, lists=20, list_bytes=20 << 40)
 
 
+def test_unbounded_over_the_two_keys_of_a_train_step():
+    """`TrainStep._lists` is `ListCache(None)` over (accumulate, distributed): the Normalizer's accumulating steps under one key, the
+    steady ones under the other.  The script is a `TrainStep(use_graph="list")` on a model that accumulates three times, whose engine
+    signature then moves twice (the owner's `invalidate` in front of the decision) and whose guard is switched on at the end
+    (`_drop_recorded`: `clear`)."""
+    ACC, STEADY = (True, False), (False, False)
+    c = ListCache(None)
+    assert [_visit(c, ACC, 1 << 40) for _ in range(3)] == ["eager", "eager", "record"] and list(c) == [ACC]
+    assert [_visit(c, STEADY, 1 << 40) for _ in range(4)] == ["eager", "eager", "record", "replay"]
+    assert list(c) == [ACC, STEADY] and c.warm == {ACC: 2, STEADY: 2}        # (no budget: the older list stays)
+    _stats(c, replayed=1, recorded=2, eager=4, lists=2, list_bytes=2 << 40)
+    c.invalidate(STEADY)                                                       # the step that finds the list stale ...
+    assert list(c) == [ACC] and c.warm == {ACC: 2, STEADY: 0}
+    assert _visit(c, STEADY) == "eager" and c.warm[STEADY] == 1                # ... is the first of the new warm-up
+    assert STEADY not in c and [_visit(c, STEADY) for _ in range(3)] == ["eager", "record", "replay"]
+    c.invalidate(STEADY)
+    assert _visit(c, STEADY, listed=False) == "eager" and c.warm[STEADY] == 0  # (a step that is not listed warms nothing up)
+    assert [_visit(c, STEADY) for _ in range(3)] == ["eager", "eager", "record"]
+    assert c[ACC].bytes == 1 << 40 and c.oversize == set() and c.evicted == {}  # the other key's list was never touched
+    _stats(c, replayed=2, recorded=4, eager=9, lists=2, list_bytes=(1 << 40) + 10)
+    c.clear()
+    assert not c and c.warm == {}
+    assert [_visit(c, STEADY) for _ in range(4)] == ["eager", "eager", "record", "replay"]
+    _stats(c, replayed=3, recorded=5, eager=11, lists=1, list_bytes=10)
+
+
 def test_the_mapping_view():
     c = ListCache(100)
     assert not c and len(c) == 0 and "a" not in c and list(c) == []

@@ -281,7 +281,8 @@ def _run_modes(mode, changes=False):
     # up, step 3 records the list - the hipGraph mode captures on a key's first step - steps 4 and 5 replay)
     for _ in range(4):
         ts.step()
-    recorded = None if not mode else dict(ts._graphs)
+    kept = ts._lists if mode == "list" else ts._captures       # (command lists; hipGraph captures)
+    recorded = None if not mode else dict(kept)
     if changes:
         obs.weight = 3e5
         obs.set_values(values * 1.05)
@@ -290,10 +291,11 @@ def _run_modes(mode, changes=False):
         obs.set_weights(weights * 0.5)
     ts.step()
     if recorded is not None:
-        assert len(recorded) >= 1 and ts._graphs.keys() == recorded.keys()
-        assert all(ts._graphs[k] is recorded[k] for k in recorded)       # replayed, never re-recorded
+        assert len(recorded) >= 1 and kept.keys() == recorded.keys()
+        assert all(kept[k] is recorded[k] for k in recorded)      # replayed, never re-recorded
         if mode == "list":
-            assert all(len(ts._graphs[k][0]) == len(recorded[k][0]) for k in recorded)
+            assert all(kept[k].cl is recorded[k].cl and len(kept[k].cl) == len(recorded[k].cl) for k in recorded)
+            assert ts.stats()["recorded"] == len(recorded)
     return _state(ts)
 
 
@@ -323,8 +325,8 @@ def test_the_list_of_a_step_without_observations_is_two_launches_shorter():
         ts = TrainStep(_model(), graphs, lr=5e-5, use_graph="list", observations=obs)
         for _ in range(4):                     # (one accumulating step, two warm-ups, the recording)
             ts.step()
-        (entry,) = ts._graphs.values()
-        counts.append(len(entry[0]))
+        (entry,) = ts._lists.values()
+        counts.append(len(entry.cl))
     print("recorded commands per step without / with observations:", counts)
     assert counts[1] == counts[0] + 2
 

@@ -393,7 +393,7 @@ def test_trainstep_follows_backward_then_adamw_with_the_same_groups(mode):
     losses = [float(ts.step()) for _ in range(STEPS)]
     torch.cuda.synchronize()
     if mode == "list":
-        assert any(isinstance(k, tuple) and k[0] == "list" for k in ts._graphs)
+        assert len(ts._lists) >= 1
     for a, b in zip(want_losses, losses):
         assert abs(a - b) < 1e-5 * abs(a), (a, b)
     got = _start_values(model)
@@ -422,15 +422,15 @@ def test_new_group_values_reach_a_recorded_list():
         ts = TrainStep(model, _graphs(), lr=LR, use_graph=mode, weight_decay=WD, param_groups=_param_groups(model))
         for _ in range(3):
             ts.step()
-        recorded = {k: v[0] for k, v in ts._graphs.items()}
-        assert bool(recorded) == (mode == "list")
+        recorded = {k: e.cl for k, e in ts._lists.items()}
+        assert bool(recorded) == (mode == "list") and ts.stats()["recorded"] == len(recorded)
         before = _named_bits(ts)
         ts.set_group(2, lr_scale=0.5, weight_decay=0.2)
         ts.lr = 2.5e-4
         assert ts.param_groups[2]["lr"] == 2.5e-4 * 0.5 and ts.param_groups[2]["weight_decay"] == 0.2
         losses = [ts.step().clone() for _ in range(2)]
-        assert {k: v[0] for k, v in ts._graphs.items()}.keys() == recorded.keys()
-        assert all(ts._graphs[k][0] is v for k, v in recorded.items())      # nothing was recorded again
+        assert ts._lists.keys() == recorded.keys() and ts.stats()["recorded"] == len(recorded)
+        assert all(ts._lists[k].cl is v for k, v in recorded.items())      # nothing was recorded again
         out[mode] = (_named_bits(ts), [l.cpu() for l in losses], before)
     assert _same(out[False][2], out["list"][2])
     assert _same(out[False][0], out["list"][0])
@@ -557,7 +557,7 @@ def test_groups_with_guard_accumulation_and_averaged_weights():
         ts.step()
         assert _same(before, bits()) == (k % 2 == 0), k
     assert float(ts.adam_state[0]) == 4.0 and ts.ema_stats()["updates"] == 4
-    assert any(isinstance(k, tuple) and k[0] == "list" for k in ts._graphs)
+    assert len(ts._lists) >= 1
     st = ts.guard_stats()
     assert st["clipped"] == 4 and st["decision"] == 1 and st["norm"] > 1e-3
     avg = ts.ema_parameters()
@@ -596,7 +596,7 @@ def test_grouped_step_in_hipgraph_mode_matches_eager():
                 ts.lr = 2.5e-4
             losses.append(ts.step().clone())
         if mode:
-            assert 1 <= len(ts._graphs) <= 2         # a capture per (accumulate, distributed) key: nothing captured again
+            assert 1 <= len(ts._captures) <= 2 and not ts._lists        # a capture per (accumulate, distributed) key: nothing captured again
         out[mode] = (_named_bits(ts), [l.cpu() for l in losses])
     assert _same(out[False][0], out[True][0])
     assert all(torch.equal(a, b) for a, b in zip(out[False][1], out[True][1]))

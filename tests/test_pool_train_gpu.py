@@ -243,7 +243,7 @@ def test_a_byte_budget_for_one_list_does_not_record_on_every_visit():
     seq = [[0], [1]] * 10
     ref_losses, ref_ts, _ = _reference_run(_three_size_pool(), seq)
     probe_losses, probe, _ = _pool_run(_three_size_pool(), seq[:6], max_graphs=1, use_graph="list")
-    one, two = sorted(e.bytes for e in probe._graphs.values())
+    one, two = sorted(e.bytes for e in probe._lists.values())
     losses, ts, _ = _pool_run(_three_size_pool(), seq, max_graphs=1, use_graph="list", max_list_bytes=two + one // 2)
     assert losses == ref_losses and torch.equal(ts.flat_p, ref_ts.flat_p)
     st = ts.stats()
@@ -392,7 +392,7 @@ def test_normalizer_flip_uses_a_list_per_accumulate_value():
     assert float(model.node_norm.num_accumulations) == 6.0
     st = ts.stats()
     assert st["lists"] == 2 and st["recorded"] == 2 and st["replayed"] == 4 and st["eager"] == 4, st
-    assert sorted(k[1] for k in ts._graphs) == [False, True]
+    assert sorted(k[1] for k in ts._lists) == [False, True]
 
 
 def test_unsupported_modes_are_refused():

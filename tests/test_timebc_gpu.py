@@ -532,8 +532,8 @@ def test_march_without_time_bc_records_one_launch_less():
         ms = _march(None, tbc)
         for _ in range(4):
             ms.step()
-        (entry,) = [v for v in ms._graphs.values()]
-        lens[name] = len(entry[0])
+        (entry,) = ms._lists.values()
+        lens[name] = len(entry.cl)
     assert lens["driven"] == lens["plain"] + 1, lens
 
 
