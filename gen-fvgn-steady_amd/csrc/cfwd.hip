@@ -49,14 +49,15 @@ __device__ __forceinline__ void cf_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-template <int KT0, int TG, int NW>
+template <int KT0, int TG, int NW, bool NRW>
 struct CfLds {
   static constexpr int KTB = KT0 > 4 ? KT0 : 4;
   static constexpr int B0 = 0;                          // the input fragments; later the third layer's input
   static constexpr int B1 = TG * KTB * 2048;            // the second layer's input
   static constexpr int SINV = B1 + TG * 8192;           // float [TG * 16]: 1 / row scale of the input rows
   static constexpr int LNP = SINV + TG * 64;            // float2 [TG * 16][NW]: per-wave (mean, M2) of a row
-  static constexpr int TOTAL = LNP + TG * 16 * NW * 8;
+  static constexpr int LNC = LNP + TG * 16 * NW * 8;    // float [TG * 16][NW]: hidden < 128 - the wave's count of non-zero entries
+  static constexpr int TOTAL = LNC + (NRW ? TG * 16 * NW * 4 : 0);
 };
 
 // KT0: k-groups of the first layer (K / 32, zero padded); N0: 16-column pieces of segment 0 (the rest from segment 1);
@@ -66,18 +67,20 @@ struct CfLds {
 // flight per tile, half the instruction stream per wave; the columns a wave produces are then HALF a k-group of the next layer)
 // FINLN = false: no LayerNorm and a NARROW last layer (the decoder, EPD.py:199-219: 128 -> 128 -> 128 -> 3): the wave that owns
 // columns 0 .. 15 runs the last layer alone and stores the N <= 16 valid columns (any output row stride)
-template <int KT0, int N0, int TG, bool PADD, int LOWP, bool RAGIN, int NW = 4, bool FINLN = true>
+// NRW: the instantiation for hidden < 128 (its LayerNorm statistics: below); the 128-wide model runs the NRW = false kernels alone
+template <int KT0, int N0, int TG, bool PADD, int LOWP, bool RAGIN, int NW = 4, bool FINLN = true, bool NRW = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void cfwd_kernel(const gfv_rowtile_args_t A, int* status) {
   static_assert(TG == 2 || TG == 4, "one loader wave per group");
   static_assert(NW == 4 || NW == 8, "32 or 16 columns per wave");
   constexpr int NT = 8 / NW;   // n-tiles per wave
-  using LY = CfLds<KT0, TG, NW>;
+  using LY = CfLds<KT0, TG, NW, NRW>;
   constexpr bool BF = LOWP == 2;
   __shared__ __attribute__((aligned(16))) char lds[LY::TOTAL];
   char* b0 = lds + LY::B0;
   char* b1 = lds + LY::B1;
   float* sinv = reinterpret_cast<float*>(lds + LY::SINV);
   float* lnp = reinterpret_cast<float*>(lds + LY::LNP);
+  float* lnc = reinterpret_cast<float*>(lds + LY::LNC);
 
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
@@ -301,9 +304,10 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void cfwd_kernel(const gf
   mma(b0, std::integral_constant<int, 4>{});
   // LayerNorm width: a narrower model runs zero padded to 128 columns, and WHERE its h real columns sit depends on the tensor
   // (node latents 0 .. h - 1, the two halves of an edge latent at 0 and 64: FVMmodel/padding.py) - so the statistics are taken
-  // over all 128 columns, whose padded ones are exactly zero, and corrected: mean_h = sum / h,
-  // sum_real (y - mean_h)^2 = M2_128 + 128 (mean_128 - mean_h)^2 - (128 - h) mean_h^2   (tchain_kernel.h ln_stats: the same sums)
-  const int hcols = (A.hidden > 0 && A.hidden < 128) ? A.hidden : 128;
+  // over the NON-ZERO entries of all 128 columns, whose padded ones are exactly zero: mean_h = sum / h,
+  // sum_real (y - mean_h)^2 = sum_waves [M2_w + n_w (mean_w - mean_h)^2] + (h - sum n_w) mean_h^2, every term non-negative
+  // (gfv_common.h gfv_lnq_*, tchain_kernel.h ln_stats: the same rule)
+  const int hcols = NRW ? A.hidden : 128;
   float y[TG][4 * NT];
 #pragma unroll
   for (int q = 0; q < TG; ++q) {
@@ -322,26 +326,57 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void cfwd_kernel(const gf
         s += v[r];
       }
     }
-    const float mw = row_sum(s) * (1.0f / (16.0f * NT));   // this wave's 16 NT columns
-    float m2 = 0.f;
+    float mw, m2 = 0.f;
+    if constexpr (!NRW) {
+      mw = row_sum(s) * (1.0f / (16.0f * NT));   // this wave's 16 NT columns
 #pragma unroll
-    for (int e = 0; e < 4 * NT; ++e) {
-      const float d = y[q][e] - mw;
-      m2 += d * d;
+      for (int e = 0; e < 4 * NT; ++e) {
+        const float d = y[q][e] - mw;
+        m2 += d * d;
+      }
+      m2 = row_sum(m2);
+    } else {   // the wave's NON-ZERO entries, with their count (zeros: padding, or real columns that the combination counts)
+      float cn = 0.f;
+#pragma unroll
+      for (int e = 0; e < 4 * NT; ++e) cn += y[q][e] != 0.f ? 1.f : 0.f;
+      cn = row_sum(cn);
+      mw = cn > 0.f ? row_sum(s) / cn : 0.f;
+#pragma unroll
+      for (int e = 0; e < 4 * NT; ++e) {
+        const float d = y[q][e] - mw;
+        m2 += y[q][e] != 0.f ? d * d : 0.f;
+      }
+      m2 = row_sum(m2);
+      if (g == 0) lnc[(q * 16 + j) * NW + w] = cn;
     }
-    m2 = row_sum(m2);
     if (g == 0) *reinterpret_cast<float2*>(lnp + ((q * 16 + j) * NW + w) * 2) = make_float2(mw, m2);
   }
   cf_barrier();
   {
-    const float inv_h = 1.0f / (float)hcols, npad = (float)(128 - hcols);
+    const float inv_h = 1.0f / (float)hcols;
 #pragma unroll
     for (int q = 0; q < TG; ++q) {
       const int row = row0 + 16 * q + j;
       const bool live = q < ngt && row < A.M;
       const float4* pp = reinterpret_cast<const float4*>(lnp + (q * 16 + j) * 2 * NW);
       float m128, m2a;   // mean and sum of squared deviations over all 128 columns (Chan's combination of the waves' pairs)
-      if constexpr (NW == 4) {
+      if constexpr (NRW) {   // Chan's combination with the waves' counts, about the mean of the h real columns
+        const float2* pw = reinterpret_cast<const float2*>(pp);
+        const float* cw = lnc + (q * 16 + j) * NW;
+        float sum = 0.f, cn = 0.f;
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+          sum += cw[v] * pw[v].x;
+          cn += cw[v];
+        }
+        m128 = sum * inv_h;
+        m2a = ((float)hcols - cn) * (m128 * m128);   // real columns that are exactly zero: deviation -mean each
+#pragma unroll
+        for (int v = 0; v < NW; ++v) {
+          const float e = pw[v].x - m128;
+          m2a += pw[v].y + cw[v] * (e * e);
+        }
+      } else if constexpr (NW == 4) {
         const float4 p0 = pp[0], p1 = pp[1];   // (mean, M2) of waves 0, 1 | 2, 3
         m128 = ((p0.x + p0.z) + (p1.x + p1.z)) * 0.25f;
         const float e0 = p0.x - m128, e1 = p0.z - m128, e2 = p1.x - m128, e3 = p1.z - m128;
@@ -354,9 +389,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : 2) void cfwd_kernel(const gf
         m2a = (((p0.y + p0.w) + (p1.y + p1.w)) + ((p2.y + p2.w) + (p3.y + p3.w))) +
               16.0f * (((e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3)) + ((e4 * e4 + e5 * e5) + (e6 * e6 + e7 * e7)));
       }
-      const float mean = hcols == 128 ? m128 : (m128 * 128.0f) * inv_h;
-      const float dm = m128 - mean;
-      const float m2 = hcols == 128 ? m2a : (m2a + 128.0f * dm * dm) - npad * (mean * mean);
+      const float mean = m128, m2 = m2a;
       const float rstd = rsqrtf(m2 * inv_h + 1e-5f);   // nn.LayerNorm eps (EPD.py:32)
       if (A.fin_stats && live && w == 0 && g == 0) *reinterpret_cast<float2*>(A.fin_stats + 2 * (size_t)row) = make_float2(mean, rstd);
 #pragma unroll
@@ -387,6 +420,14 @@ void cf_launch(const gfv_rowtile_args_t& a, int lowp, hipStream_t stream) {
   constexpr int tg = 2;
   const int tiles = (a.M + 16 * tg - 1) / (16 * tg);
   const dim3 grid(PADD ? gfv_xcd_grid(tiles) : tiles), blk(512);
+  if constexpr (FINLN) {
+    if (ln_is_narrow(a.hidden)) {   // a model of hidden < 128: the NRW twins
+      if (lowp == 2) GFV_LAUNCH((cfwd_kernel<KT0, N0, 2, PADD, 2, RAGIN, 8, FINLN, true>), grid, blk, 0, stream, a, st);
+      else if (lowp) GFV_LAUNCH((cfwd_kernel<KT0, N0, 2, PADD, 1, RAGIN, 8, FINLN, true>), grid, blk, 0, stream, a, st);
+      else GFV_LAUNCH((cfwd_kernel<KT0, N0, 2, PADD, 0, RAGIN, 8, FINLN, true>), grid, blk, 0, stream, a, st);
+      return;
+    }
+  }
   if (lowp == 2) GFV_LAUNCH((cfwd_kernel<KT0, N0, 2, PADD, 2, RAGIN, 8, FINLN>), grid, blk, 0, stream, a, st);
   else if (lowp) GFV_LAUNCH((cfwd_kernel<KT0, N0, 2, PADD, 1, RAGIN, 8, FINLN>), grid, blk, 0, stream, a, st);
   else GFV_LAUNCH((cfwd_kernel<KT0, N0, 2, PADD, 0, RAGIN, 8, FINLN>), grid, blk, 0, stream, a, st);

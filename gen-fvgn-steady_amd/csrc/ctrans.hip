@@ -27,15 +27,43 @@ constexpr float CT_SH_LIMIT = 2048.0f;
 
 __device__ __forceinline__ void ct_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-struct CtLds {
+template <bool NRW>
+struct CtLdsT {
   static constexpr int B0 = 0;                       // out_x fragments: 2 groups x 4 k-groups x 2 KB
   static constexpr int B1 = 16384;                   // LayerNorm output fragments
   static constexpr int B2 = 32768;                   // gelu(z) fragments: 2 groups x 8 k-groups x 2 KB
   static constexpr int SINV = 65536;                 // float [32]: 1 / row scale of the input rows
   static constexpr int LNP = SINV + 128;             // float2 [32][8]: per-wave (mean, M2) of a row
   static constexpr int BND = LNP + 32 * 8 * 8;       // float [8]: per-wave bound of |LayerNorm output|
-  static constexpr int TOTAL = BND + 32;
+  static constexpr int LNC = BND + 32;               // float [32][8]: hidden < 128 - the wave's count of non-zero entries
+  static constexpr int TOTAL = LNC + (NRW ? 32 * 8 * 4 : 0);
 };
+
+// LayerNorm at hidden < 128 (cfwd.hip, gfv_common.h gfv_lnq_*: the same rule).  A wave's 16 columns of a row: mean and M2 of
+// its NON-ZERO entries and their count - the zeros are padding, or real columns that the combination counts
+__device__ __forceinline__ void ct_part_nz(float x0, float x1, float x2, float x3, float& mw, float& m2, float& cn) {
+  cn = row_sum(((x0 != 0.f ? 1.f : 0.f) + (x1 != 0.f ? 1.f : 0.f)) + ((x2 != 0.f ? 1.f : 0.f) + (x3 != 0.f ? 1.f : 0.f)));
+  mw = cn > 0.f ? row_sum((x0 + x1) + (x2 + x3)) / cn : 0.f;
+  const float d0 = x0 - mw, d1 = x1 - mw, d2 = x2 - mw, d3 = x3 - mw;
+  m2 = row_sum(((x0 != 0.f ? d0 * d0 : 0.f) + (x1 != 0.f ? d1 * d1 : 0.f)) + ((x2 != 0.f ? d2 * d2 : 0.f) + (x3 != 0.f ? d3 * d3 : 0.f)));
+}
+// Chan's combination of the eight waves' (mean, M2, count) about the mean of the h real columns; the h - sum(count) real
+// columns that are exactly zero deviate by -mean each.  Every term is non-negative.
+__device__ __forceinline__ void ct_combine_nz(const float2* pw, const float* cw, int hcols, float inv_h, float& mean, float& m2) {
+  float sum = 0.f, cn = 0.f;
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    sum += cw[v] * pw[v].x;
+    cn += cw[v];
+  }
+  mean = sum * inv_h;
+  m2 = ((float)hcols - cn) * (mean * mean);
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    const float e = pw[v].x - mean;
+    m2 += pw[v].y + cw[v] * (e * e);
+  }
+}
 
 struct CtArgs {
   const float* x; const float* res;
@@ -48,10 +76,12 @@ struct CtArgs {
 
 // SAVE = false: the forward-only form (fx1 == z == NULL) - the two saved tensors are not stored; nothing else differs (the
 // residual rows already stay in registers)
-template <int LOWP, bool SAVE>
+// NRW: the instantiation for hidden < 128; the 128-wide model runs the NRW = false kernels alone
+template <int LOWP, bool SAVE, bool NRW = false>
 __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int* status) {
   constexpr bool BF = LOWP == 2;
   constexpr int TG = 2;
+  using CtLds = CtLdsT<NRW>;
   __shared__ __attribute__((aligned(16))) char lds[CtLds::TOTAL];
   char* b0 = lds + CtLds::B0;
   char* b1 = lds + CtLds::B1;
@@ -59,6 +89,7 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
   float* sinv = reinterpret_cast<float*>(lds + CtLds::SINV);
   float* lnp = reinterpret_cast<float*>(lds + CtLds::LNP);
   float* bnd = reinterpret_cast<float*>(lds + CtLds::BND);
+  float* lnc = reinterpret_cast<float*>(lds + CtLds::LNC);
 
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
@@ -153,6 +184,7 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
       bl[n][T] = LOWP ? bh[n][T] : im[T * 1024 + 64];
     }
   }
+  const int hcols = (A.hidden > 0 && A.hidden < 128) ? A.hidden : 128;   // the LayerNorm width
   float fx[TG][4];
 #pragma unroll
   for (int q = 0; q < TG; ++q) {
@@ -162,9 +194,16 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
     fx[q][0] = (acc[q][0] * si) * invw + bA.x + rres[q].x; fx[q][1] = (acc[q][1] * si) * invw + bA.y + rres[q].y;
     fx[q][2] = (acc[q][2] * si) * invw + bA.z + rres[q].z; fx[q][3] = (acc[q][3] * si) * invw + bA.w + rres[q].w;
     if (SAVE && live) st4(A.fx1 + (size_t)row * 128 + c0, fx[q]);
-    const float mw = row_sum((fx[q][0] + fx[q][1]) + (fx[q][2] + fx[q][3])) * (1.0f / 16.0f);   // this wave's 16 columns
-    const float d0 = fx[q][0] - mw, d1 = fx[q][1] - mw, d2 = fx[q][2] - mw, d3 = fx[q][3] - mw;
-    const float m2 = row_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
+    float mw, m2;
+    if constexpr (!NRW) {
+      mw = row_sum((fx[q][0] + fx[q][1]) + (fx[q][2] + fx[q][3])) * (1.0f / 16.0f);   // this wave's 16 columns
+      const float d0 = fx[q][0] - mw, d1 = fx[q][1] - mw, d2 = fx[q][2] - mw, d3 = fx[q][3] - mw;
+      m2 = row_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
+    } else {
+      float cn;
+      ct_part_nz(fx[q][0], fx[q][1], fx[q][2], fx[q][3], mw, m2, cn);
+      if (g == 0) lnc[(q * 16 + j) * 8 + w] = cn;
+    }
     if (g == 0) *reinterpret_cast<float2*>(lnp + ((q * 16 + j) * 8 + w) * 2) = make_float2(mw, m2);
   }
   ct_barrier();
@@ -173,21 +212,23 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
   {
     const float4 ba = *reinterpret_cast<const float4*>(bnd), bb = *reinterpret_cast<const float4*>(bnd + 4);
     sB = gfv_pow2_scale(fmaxf(fmaxf(fmaxf(ba.x, ba.y), fmaxf(ba.z, ba.w)), fmaxf(fmaxf(bb.x, bb.y), fmaxf(bb.z, bb.w))));
-    const int hcols = (A.hidden > 0 && A.hidden < 128) ? A.hidden : 128;
-    const float inv_h = 1.0f / (float)hcols, npad = (float)(128 - hcols);
+    const float inv_h = 1.0f / (float)hcols;
 #pragma unroll
     for (int q = 0; q < TG; ++q) {
       const float4* pp = reinterpret_cast<const float4*>(lnp + (q * 16 + j) * 16);
-      const float4 p0 = pp[0], p1 = pp[1], p2 = pp[2], p3 = pp[3];   // (mean, M2) x 8 waves
-      const float m128 = (((p0.x + p0.z) + (p1.x + p1.z)) + ((p2.x + p2.z) + (p3.x + p3.z))) * 0.125f;
-      const float e0 = p0.x - m128, e1 = p0.z - m128, e2 = p1.x - m128, e3 = p1.z - m128, e4 = p2.x - m128, e5 = p2.z - m128,
-                  e6 = p3.x - m128, e7 = p3.z - m128;
-      const float m2a = (((p0.y + p0.w) + (p1.y + p1.w)) + ((p2.y + p2.w) + (p3.y + p3.w))) +
-                        16.0f * (((e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3)) + ((e4 * e4 + e5 * e5) + (e6 * e6 + e7 * e7)));
-      // (a narrower model: statistics over all 128 columns, whose padded ones are exactly zero, corrected - cfwd.hip)
-      const float mean = hcols == 128 ? m128 : (m128 * 128.0f) * inv_h;
-      const float dm = m128 - mean;
-      const float m2 = hcols == 128 ? m2a : (m2a + 128.0f * dm * dm) - npad * (mean * mean);
+      float mean, m2;
+      if constexpr (!NRW) {
+        const float4 p0 = pp[0], p1 = pp[1], p2 = pp[2], p3 = pp[3];   // (mean, M2) x 8 waves
+        const float m128 = (((p0.x + p0.z) + (p1.x + p1.z)) + ((p2.x + p2.z) + (p3.x + p3.z))) * 0.125f;
+        const float e0 = p0.x - m128, e1 = p0.z - m128, e2 = p1.x - m128, e3 = p1.z - m128, e4 = p2.x - m128, e5 = p2.z - m128,
+                    e6 = p3.x - m128, e7 = p3.z - m128;
+        const float m2a = (((p0.y + p0.w) + (p1.y + p1.w)) + ((p2.y + p2.w) + (p3.y + p3.w))) +
+                          16.0f * (((e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3)) + ((e4 * e4 + e5 * e5) + (e6 * e6 + e7 * e7)));
+        mean = m128;
+        m2 = m2a;
+      } else {   // a narrower model: the non-zero entries with their counts (ct_combine_nz)
+        ct_combine_nz(reinterpret_cast<const float2*>(pp), lnc + (q * 16 + j) * 8, hcols, inv_h, mean, m2);
+      }
       const float rstd = rsqrtf(m2 * inv_h + 1e-5f);
       const float l0 = (fx[q][0] - mean) * rstd * gam.x + bet.x, l1 = (fx[q][1] - mean) * rstd * gam.y + bet.y;
       const float l2 = (fx[q][2] - mean) * rstd * gam.z + bet.z, l3 = (fx[q][3] - mean) * rstd * gam.w + bet.w;
@@ -296,7 +337,8 @@ __global__ __launch_bounds__(512, 2) void ctrans_fwd_kernel(const CtArgs A, int*
 // 128-row-block kernel writes it); g_z steps down from the tile's largest row by linear_post's guaranteed growth (row 1-norms of this
 // wave's slice of the image, the workgroup's maximum through LDS - colchain_kernel.h); g_fx1 takes its scale from the bound of the
 // LayerNorm backward (rstd max|v gamma| (2 + sqrt(127)) + max|g|, colchain_kernel.h P0b).  ln_partial: one row per 32 rows here.
-struct CtLdsB {
+template <bool NRW>
+struct CtLdsBT {
   static constexpr int B0 = 0;                       // g fragments (2 groups x 4 k-groups x 2 KB); later g_fx1's
   static constexpr int B1 = 16384;                   // g_z fragments: 2 groups x 8 k-groups x 2 KB
   static constexpr int SINV = 49152;                 // float [32]
@@ -305,7 +347,8 @@ struct CtLdsB {
   static constexpr int SMAX = PART + 2048;           // float [8]: per-wave bound term of the LayerNorm backward
   static constexpr int NRM = SMAX + 32;              // float [8]: per-wave largest row 1-norm of linear_post^T's slice
   static constexpr int SMIN = NRM + 32;              // float [2]: smallest row scale of each group
-  static constexpr int TOTAL = SMIN + 16;
+  static constexpr int LNC = SMIN + 16;              // float [32][8]: hidden < 128 - the wave's count of non-zero entries
+  static constexpr int TOTAL = LNC + (NRW ? 32 * 8 * 4 : 0);
 };
 
 struct CtBwdArgs {
@@ -317,16 +360,19 @@ struct CtBwdArgs {
   int M, hidden;
 };
 
-template <int LOWP>
+template <int LOWP, bool NRW = false>
 __global__ __launch_bounds__(512, 2) void ctrans_bwd_kernel(const CtBwdArgs A, int* status) {
   constexpr bool BF = LOWP == 2;
   constexpr int TG = 2;
+  using CtLdsB = CtLdsBT<NRW>;
   __shared__ __attribute__((aligned(16))) char lds[CtLdsB::TOTAL];
   char* b0 = lds + CtLdsB::B0;
   char* b1 = lds + CtLdsB::B1;
   float* sinv = reinterpret_cast<float*>(lds + CtLdsB::SINV);
   float* lnp = reinterpret_cast<float*>(lds + CtLdsB::LNP);
   float* part = reinterpret_cast<float*>(lds + CtLdsB::PART);
+  float* lnc = reinterpret_cast<float*>(lds + CtLdsB::LNC);
+  const int hcols = (A.hidden > 0 && A.hidden < 128) ? A.hidden : 128;   // the LayerNorm width
   float* smax = reinterpret_cast<float*>(lds + CtLdsB::SMAX);
   float* nrm = reinterpret_cast<float*>(lds + CtLdsB::NRM);
   float* smin = reinterpret_cast<float*>(lds + CtLdsB::SMIN);
@@ -436,9 +482,16 @@ __global__ __launch_bounds__(512, 2) void ctrans_bwd_kernel(const CtBwdArgs A, i
   }
 #pragma unroll
   for (int q = 0; q < TG; ++q) {
-    const float mw = row_sum((yq[q].x + yq[q].y) + (yq[q].z + yq[q].w)) * (1.0f / 16.0f);
-    const float d0 = yq[q].x - mw, d1 = yq[q].y - mw, d2 = yq[q].z - mw, d3 = yq[q].w - mw;
-    const float m2 = row_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
+    float mw, m2;
+    if constexpr (!NRW) {
+      mw = row_sum((yq[q].x + yq[q].y) + (yq[q].z + yq[q].w)) * (1.0f / 16.0f);
+      const float d0 = yq[q].x - mw, d1 = yq[q].y - mw, d2 = yq[q].z - mw, d3 = yq[q].w - mw;
+      m2 = row_sum((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
+    } else {   // (the forward launch's rule, so that both form the same statistics)
+      float cn;
+      ct_part_nz(yq[q].x, yq[q].y, yq[q].z, yq[q].w, mw, m2, cn);
+      if (g == 0) lnc[(q * 16 + j) * 8 + w] = cn;
+    }
     if (g == 0) *reinterpret_cast<float2*>(lnp + ((q * 16 + j) * 8 + w) * 2) = make_float2(mw, m2);
   }
   ct_barrier();
@@ -550,8 +603,7 @@ __global__ __launch_bounds__(512, 2) void ctrans_bwd_kernel(const CtBwdArgs A, i
   }
   float gg[TG][4], xh_[TG][4], rs[TG];
   {
-    const int hcols = (A.hidden > 0 && A.hidden < 128) ? A.hidden : 128;
-    const float inv_h = 1.0f / (float)hcols, npad = (float)(128 - hcols);
+    const float inv_h = 1.0f / (float)hcols;
     const float isg = 1.0f / s_gz;
     float dgam[4] = {0.f, 0.f, 0.f, 0.f}, dbet[4] = {0.f, 0.f, 0.f, 0.f};
     float bmax = 0.f;
@@ -562,15 +614,19 @@ __global__ __launch_bounds__(512, 2) void ctrans_bwd_kernel(const CtBwdArgs A, i
       const float lf = (q < ngt && row < A.M) ? 1.0f : 0.0f;   // rows past M must not reach the sums over rows
       // the row's statistics: Chan's combination of the eight waves' (mean, M2) pairs (written before the first barrier)
       const float4* pp = reinterpret_cast<const float4*>(lnp + (q * 16 + j) * 16);
-      const float4 p0 = pp[0], p1 = pp[1], p2 = pp[2], p3 = pp[3];
-      const float m128 = (((p0.x + p0.z) + (p1.x + p1.z)) + ((p2.x + p2.z) + (p3.x + p3.z))) * 0.125f;
-      const float e0 = p0.x - m128, e1 = p0.z - m128, e2 = p1.x - m128, e3 = p1.z - m128, e4 = p2.x - m128, e5 = p2.z - m128,
-                  e6 = p3.x - m128, e7 = p3.z - m128;
-      const float m2a = (((p0.y + p0.w) + (p1.y + p1.w)) + ((p2.y + p2.w) + (p3.y + p3.w))) +
-                        16.0f * (((e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3)) + ((e4 * e4 + e5 * e5) + (e6 * e6 + e7 * e7)));
-      const float mean = hcols == 128 ? m128 : (m128 * 128.0f) * inv_h;
-      const float dm = m128 - mean;
-      const float m2 = hcols == 128 ? m2a : (m2a + 128.0f * dm * dm) - npad * (mean * mean);
+      float mean, m2;
+      if constexpr (!NRW) {
+        const float4 p0 = pp[0], p1 = pp[1], p2 = pp[2], p3 = pp[3];
+        const float m128 = (((p0.x + p0.z) + (p1.x + p1.z)) + ((p2.x + p2.z) + (p3.x + p3.z))) * 0.125f;
+        const float e0 = p0.x - m128, e1 = p0.z - m128, e2 = p1.x - m128, e3 = p1.z - m128, e4 = p2.x - m128, e5 = p2.z - m128,
+                    e6 = p3.x - m128, e7 = p3.z - m128;
+        const float m2a = (((p0.y + p0.w) + (p1.y + p1.w)) + ((p2.y + p2.w) + (p3.y + p3.w))) +
+                          16.0f * (((e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3)) + ((e4 * e4 + e5 * e5) + (e6 * e6 + e7 * e7)));
+        mean = m128;
+        m2 = m2a;
+      } else {
+        ct_combine_nz(reinterpret_cast<const float2*>(pp), lnc + (q * 16 + j) * 8, hcols, inv_h, mean, m2);
+      }
       const float rstd = rsqrtf(m2 * inv_h + 1e-5f);
       rs[q] = rstd;
       const float y[4] = {yq[q].x, yq[q].y, yq[q].z, yq[q].w};
@@ -617,7 +673,6 @@ __global__ __launch_bounds__(512, 2) void ctrans_bwd_kernel(const CtBwdArgs A, i
     const float mx = fmaxf(fmaxf(fmaxf(ma.x, ma.y), fmaxf(ma.z, ma.w)), fmaxf(fmaxf(mb.x, mb.y), fmaxf(mb.z, mb.w)));
     // |g_fx1| <= rstd max|v gamma| (2 + sqrt(127)) + max|g|;  max|g| < 2^14 / s_tile
     s3 = gfv_pow2_scale(mx * 13.5f + 16384.0f / s_tile);
-    const int hcols = (A.hidden > 0 && A.hidden < 128) ? A.hidden : 128;
     const float inv_h = 1.0f / (float)hcols;
 #pragma unroll
     for (int q = 0; q < TG; ++q) {
@@ -689,7 +744,11 @@ int gfv_internal_ctrans_bwd_try(const gfv_trans_mlp_bwd_t* a, int form, hipStrea
               a->g_z, a->g_fx1, a->g_out_x, a->ln_partial, a->gscale, a->M, gfv_hidden_size()};
   int* st = gfv_internal_status_ptr();
   const dim3 grid((a->M + 31) / 32), blk(512);
-  if (form == 3) GFV_LAUNCH((ctrans_bwd_kernel<2>), grid, blk, 0, stream, B, st);
+  if (B.hidden > 0 && B.hidden < 128) {   // a model of hidden < 128: the NRW twins
+    if (form == 3) GFV_LAUNCH((ctrans_bwd_kernel<2, true>), grid, blk, 0, stream, B, st);
+    else if (form == 2) GFV_LAUNCH((ctrans_bwd_kernel<1, true>), grid, blk, 0, stream, B, st);
+    else GFV_LAUNCH((ctrans_bwd_kernel<0, true>), grid, blk, 0, stream, B, st);
+  } else if (form == 3) GFV_LAUNCH((ctrans_bwd_kernel<2>), grid, blk, 0, stream, B, st);
   else if (form == 2) GFV_LAUNCH((ctrans_bwd_kernel<1>), grid, blk, 0, stream, B, st);
   else GFV_LAUNCH((ctrans_bwd_kernel<0>), grid, blk, 0, stream, B, st);
   return 1;
@@ -703,7 +762,17 @@ int gfv_internal_ctrans_fwd_try(const gfv_trans_mlp_t* a, int form, hipStream_t 
            a->fx1, a->z, a->out, a->M, gfv_hidden_size()};
   int* st = gfv_internal_status_ptr();
   const dim3 grid((a->M + 31) / 32), blk(512);
-  if (a->fx1) {
+  if (B.hidden > 0 && B.hidden < 128) {   // a model of hidden < 128: the NRW twins
+    if (a->fx1) {
+      if (form == 3) GFV_LAUNCH((ctrans_fwd_kernel<2, true, true>), grid, blk, 0, stream, B, st);
+      else if (form == 2) GFV_LAUNCH((ctrans_fwd_kernel<1, true, true>), grid, blk, 0, stream, B, st);
+      else GFV_LAUNCH((ctrans_fwd_kernel<0, true, true>), grid, blk, 0, stream, B, st);
+    } else {
+      if (form == 3) GFV_LAUNCH((ctrans_fwd_kernel<2, false, true>), grid, blk, 0, stream, B, st);
+      else if (form == 2) GFV_LAUNCH((ctrans_fwd_kernel<1, false, true>), grid, blk, 0, stream, B, st);
+      else GFV_LAUNCH((ctrans_fwd_kernel<0, false, true>), grid, blk, 0, stream, B, st);
+    }
+  } else if (a->fx1) {
     if (form == 3) GFV_LAUNCH((ctrans_fwd_kernel<2, true>), grid, blk, 0, stream, B, st);
     else if (form == 2) GFV_LAUNCH((ctrans_fwd_kernel<1, true>), grid, blk, 0, stream, B, st);
     else GFV_LAUNCH((ctrans_fwd_kernel<0, true>), grid, blk, 0, stream, B, st);

@@ -180,7 +180,15 @@ __device__ __forceinline__ void dw_body(const DwLaunch& A, const gfv_dw_tile_t& 
         // row LayerNorm (eps 1e-5); the 32 lanes that share a row are an aligned half wave
         const float mean = gfv_half_sum((a.x + a.y) + (a.z + a.w)) * A.ln_inv_n;
         const float dx = a.x - mean, dy = a.y - mean, dz = a.z - mean, dw = a.w - mean;
-        const float var = (gfv_half_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)) - A.ln_npad * (mean * mean)) * A.ln_inv_n;
+        float ssq;
+        if (A.ln_npad == 0.f) {   // (uniform) the 128-wide model's arithmetic
+          ssq = gfv_half_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)) - A.ln_npad * (mean * mean);
+        } else {   // a narrower model: the rule of the kernels that wrote these rows (gfv_common.h gfv_lnq_*)
+          gfv_lnq_t z{0.f, 0.f};
+          gfv_lnq_add(z, a.x, mean); gfv_lnq_add(z, a.y, mean); gfv_lnq_add(z, a.z, mean); gfv_lnq_add(z, a.w, mean);
+          ssq = gfv_lnq_ssq(gfv_half_sum(z.q), gfv_half_sum(z.cz), A.ln_npad, mean);
+        }
+        const float var = ssq * A.ln_inv_n;
         const float rstd = rsqrtf(var + 1e-5f);
         a = make_float4(dx * rstd * gam.x + bet.x, dy * rstd * gam.y + bet.y, dz * rstd * gam.z + bet.z,
                         dw * rstd * gam.w + bet.w);
@@ -426,7 +434,15 @@ __device__ __forceinline__ void dw_body_h(const DwLaunch& A, const gfv_dw_tile_t
       } else if (T.a_op == 2) {
         const float mean = gfv_half_sum((a[p].x + a[p].y) + (a[p].z + a[p].w)) * A.ln_inv_n;
         const float dx = a[p].x - mean, dy = a[p].y - mean, dz = a[p].z - mean, dw = a[p].w - mean;
-        const float var = (gfv_half_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)) - A.ln_npad * (mean * mean)) * A.ln_inv_n;
+        float ssq;
+        if (A.ln_npad == 0.f) {   // (uniform) the 128-wide model's arithmetic
+          ssq = gfv_half_sum((dx * dx + dy * dy) + (dz * dz + dw * dw)) - A.ln_npad * (mean * mean);
+        } else {   // a narrower model (gfv_common.h gfv_lnq_*)
+          gfv_lnq_t z{0.f, 0.f};
+          gfv_lnq_add(z, a[p].x, mean); gfv_lnq_add(z, a[p].y, mean); gfv_lnq_add(z, a[p].z, mean); gfv_lnq_add(z, a[p].w, mean);
+          ssq = gfv_lnq_ssq(gfv_half_sum(z.q), gfv_half_sum(z.cz), A.ln_npad, mean);
+        }
+        const float var = ssq * A.ln_inv_n;
         const float rstd = rsqrtf(var + 1e-5f);
         a[p] = make_float4(dx * rstd * gam.x + bet.x, dy * rstd * gam.y + bet.y, dz * rstd * gam.z + bet.z,
                            dw * rstd * gam.w + bet.w);

@@ -170,7 +170,26 @@ static __device__ __forceinline__ float gfv_wave_min(float v) {
   return fminf(a, b);
 }
 
-// The weighted residual of one graph, w_p L_p + w_c L_c + w_m L_mx + w_m L_my (pre_train_Adam.py:177-184; l0 .. l3 = cont, mom_x,
+// ---- LayerNorm at hidden < 128: the sum of squared deviations of the h real columns of a zero-padded 128-column row -------
+// Padding columns are EXACTLY zero (the precondition of gfv_set_hidden_size), so no layout is needed: a non-zero entry adds
+// (x - mean)^2, every zero entry is counted, and the zeros beyond the npad = 128 - h padded ones are real columns whose
+// deviation is -mean.  Every term is non-negative.  (Through the parent revision the padded zeros were summed as (0 - mean)^2
+// and npad mean^2 taken out again: two numbers of size 128 mean^2 subtracted to obtain one of size h var.)
+// Only the npad != 0 branches use this; h = 128 keeps the plain sum at every site.
+struct gfv_lnq_t {
+  float q, cz;
+};
+static __device__ __forceinline__ void gfv_lnq_add(gfv_lnq_t& s, float x, float mean) {
+  const float d = x - mean;
+  s.q += x != 0.f ? d * d : 0.f;
+  s.cz += x == 0.f ? 1.f : 0.f;
+}
+// q, cz: the row's totals
+static __device__ __forceinline__ float gfv_lnq_ssq(float q, float cz, float npad, float mean) {
+  return q + (cz - npad) * (mean * mean);
+}
+
+// The weighted residual of one graph,w_p L_p + w_c L_c + w_m L_mx + w_m L_my (pre_train_Adam.py:177-184; l0 .. l3 = cont, mom_x,
 // mom_y, press): the argument of the training loss's logarithm (train_loss_kernel of csrc/misc.hip, the tail of the loss launch in csrc/fvm.hip) and the residual the
 // time march tests (csrc/march.hip).  ONE statement for all three, so that they cannot drift apart: fp32, every product and sum
 // rounded on its own, added left to right.

@@ -39,6 +39,13 @@ __device__ __forceinline__ float l1_row_max4(float v) {   // over the 4 lanes (g
   gfv_lane_xor32(v, a, b);
   return fmaxf(a, b);
 }
+__device__ __forceinline__ float l1_row_sum(float v) {
+  float a, b;
+  gfv_lane_xor16(v, a, b);
+  v = a + b;
+  gfv_lane_xor32(v, a, b);
+  return a + b;
+}
 
 struct Lin1Args {
   const float* seg[2];
@@ -62,7 +69,8 @@ struct Lin1Args {
 
 // KS: 32-wide k-steps (4: one 128-wide segment, 8: two); NP: 128-row passes of the image = 128-wide output chunks
 // IN_OP: 0 none, 1 GELU, 2 LayerNorm (one segment); DGELU: out = (acc) * gelu'(aux)
-template <int KS, int NP, int IN_OP, bool DGELU, int LOWP>   // LOWP: 0 three products, 1 / 2 the single-product forms (fp16 / bf16)
+// NRW: the instantiation for hidden < 128 (gfv_common.h gfv_lnq_*); the 128-wide model runs the NRW = false kernels alone
+template <int KS, int NP, int IN_OP, bool DGELU, int LOWP, bool NRW = false>   // LOWP: 0 three products, 1 / 2 the single-product forms (fp16 / bf16)
 __global__ __launch_bounds__(512, 2) void lin1_kernel(const Lin1Args A, int* status) {
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
   gfv_uint4* img = reinterpret_cast<gfv_uint4*>(lds_raw);
@@ -135,18 +143,29 @@ __global__ __launch_bounds__(512, 2) void lin1_kernel(const Lin1Args A, int* sta
     sm = a + b;
     gfv_lane_xor32(sm, a, b);
     const float mean = (a + b) * A.ln_inv_n;
-    float qq = 0.f;
+    float ssq;
+    if constexpr (!NRW) {   // the 128-wide model's arithmetic
+      float qq = 0.f;
 #pragma unroll
-    for (int T = 0; T < KS; ++T) {
-      const float d0 = v[T][0] - mean, d1 = v[T][1] - mean, d2 = v[T][2] - mean, d3 = v[T][3] - mean;
-      qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-      const float d4 = v[T][4] - mean, d5 = v[T][5] - mean, d6 = v[T][6] - mean, d7 = v[T][7] - mean;
-      qq += (d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7);
+      for (int T = 0; T < KS; ++T) {
+        const float d0 = v[T][0] - mean, d1 = v[T][1] - mean, d2 = v[T][2] - mean, d3 = v[T][3] - mean;
+        qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        const float d4 = v[T][4] - mean, d5 = v[T][5] - mean, d6 = v[T][6] - mean, d7 = v[T][7] - mean;
+        qq += (d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7);
+      }
+      gfv_lane_xor16(qq, a, b);
+      qq = a + b;
+      gfv_lane_xor32(qq, a, b);
+      ssq = (a + b) - A.ln_npad * (mean * mean);
+    } else {   // a narrower model: non-zero entries and a count of zeros (gfv_common.h gfv_lnq_*)
+      gfv_lnq_t z{0.f, 0.f};
+#pragma unroll
+      for (int T = 0; T < KS; ++T)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) gfv_lnq_add(z, v[T][e], mean);
+      ssq = gfv_lnq_ssq(l1_row_sum(z.q), l1_row_sum(z.cz), A.ln_npad, mean);
     }
-    gfv_lane_xor16(qq, a, b);
-    qq = a + b;
-    gfv_lane_xor32(qq, a, b);
-    const float rstd = rsqrtf(((a + b) - A.ln_npad * (mean * mean)) * A.ln_inv_n + 1e-5f);
+    const float rstd = rsqrtf(ssq * A.ln_inv_n + 1e-5f);
 #pragma unroll
     for (int T = 0; T < KS; ++T) {
       const float4 ga0 = *reinterpret_cast<const float4*>(A.gamma + 32 * T + 4 * g), ga1 = *reinterpret_cast<const float4*>(A.gamma + 32 * T + 16 + 4 * g);
@@ -254,7 +273,7 @@ struct Lin1LnbArgs {
   float* ln_partial;     // [n_tiles, 2, 128]
   int n_tiles;
 };
-template <int LOWP>
+template <int LOWP, bool NRW = false>
 __global__ __launch_bounds__(512, 2) void lin1_lnbwd_kernel(const Lin1LnbArgs B, int* status) {
   constexpr int KS = 8;
   const Lin1Args& A = B.a;
@@ -339,16 +358,27 @@ __global__ __launch_bounds__(512, 2) void lin1_lnbwd_kernel(const Lin1LnbArgs B,
   sm = a + b;
   gfv_lane_xor32(sm, a, b);
   const float mean = (a + b) * A.ln_inv_n;
-  float qq = 0.f;
+  float ssq;
+  if constexpr (!NRW) {   // the 128-wide model's arithmetic
+    float qq = 0.f;
 #pragma unroll
-  for (int nt = 0; nt < 8; ++nt) {
-    const float d0 = y[nt][0] - mean, d1 = y[nt][1] - mean, d2 = y[nt][2] - mean, d3 = y[nt][3] - mean;
-    qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    for (int nt = 0; nt < 8; ++nt) {
+      const float d0 = y[nt][0] - mean, d1 = y[nt][1] - mean, d2 = y[nt][2] - mean, d3 = y[nt][3] - mean;
+      qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    gfv_lane_xor16(qq, a, b);
+    qq = a + b;
+    gfv_lane_xor32(qq, a, b);
+    ssq = (a + b) - A.ln_npad * (mean * mean);
+  } else {   // a narrower model (gfv_common.h gfv_lnq_*)
+    gfv_lnq_t z{0.f, 0.f};
+#pragma unroll
+    for (int nt = 0; nt < 8; ++nt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gfv_lnq_add(z, y[nt][r], mean);
+    ssq = gfv_lnq_ssq(l1_row_sum(z.q), l1_row_sum(z.cz), A.ln_npad, mean);
   }
-  gfv_lane_xor16(qq, a, b);
-  qq = a + b;
-  gfv_lane_xor32(qq, a, b);
-  const float rstd = rsqrtf(((a + b) - A.ln_npad * (mean * mean)) * A.ln_inv_n + 1e-5f);
+  const float rstd = rsqrtf(ssq * A.ln_inv_n + 1e-5f);
   const float livef = live ? 1.0f : 0.0f;   // rows past M must not reach the (dgamma, dbeta) sums
   float vv[8][4], dgam[8][4], dbet[8][4];
   float s1 = 0.f, s2 = 0.f;
@@ -669,6 +699,12 @@ int gfv_internal_lin1_try(const gfv_rowtile_args_t* a, int lowp, hipStream_t str
 #define L1_LNB(LP)                                                                                               \
   do {                                                                                                           \
     static std::atomic<unsigned long long> done{0};                                                              \
+    static std::atomic<unsigned long long> done_n{0};                                                            \
+    if (B.a.ln_npad != 0.f) {   /* a model of hidden < 128: the NRW twin */                                      \
+      if (!l1_dyn_lds(reinterpret_cast<const void*>(&lin1_lnbwd_kernel<LP, true>), 131072, done_n)) return 0;    \
+      GFV_LAUNCH((lin1_lnbwd_kernel<LP, true>), grid, blk, 131072, stream, B, st);                               \
+      break;                                                                                                     \
+    }                                                                                                            \
     if (!l1_dyn_lds(reinterpret_cast<const void*>(&lin1_lnbwd_kernel<LP>), 131072, done)) return 0;              \
     GFV_LAUNCH((lin1_lnbwd_kernel<LP>), grid, blk, 131072, stream, B, st);                               \
   } while (0)
@@ -740,6 +776,14 @@ int gfv_internal_lin1_try(const gfv_rowtile_args_t* a, int lowp, hipStream_t str
 #define L1_ONE(KS, NP, IOP, DG, LP)                                                                                             \
   do {                                                                                                                          \
     static std::atomic<unsigned long long> done{0};                                                                             \
+    if constexpr ((IOP) == 2) {   /* the LayerNorm prologue of a model of hidden < 128: the NRW twin */                         \
+      static std::atomic<unsigned long long> done_n{0};                                                                         \
+      if (A.ln_npad != 0.f) {                                                                                                   \
+        if (!l1_dyn_lds(reinterpret_cast<const void*>(&lin1_kernel<KS, NP, IOP, DG, LP, true>), (NP) * (KS) * 16384, done_n)) return 0; \
+        GFV_LAUNCH((lin1_kernel<KS, NP, IOP, DG, LP, true>), grid, blk, (size_t)(NP) * (KS) * 16384, stream, A, st);            \
+        break;                                                                                                                  \
+      }                                                                                                                         \
+    }                                                                                                                           \
     if (!l1_dyn_lds(reinterpret_cast<const void*>(&lin1_kernel<KS, NP, IOP, DG, LP>), (NP) * (KS) * 16384, done)) return 0;     \
     GFV_LAUNCH((lin1_kernel<KS, NP, IOP, DG, LP>), grid, blk, (size_t)(NP) * (KS) * 16384, stream, A, st);              \
   } while (0)

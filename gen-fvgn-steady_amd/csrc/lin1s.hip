@@ -61,7 +61,8 @@ struct L1sLds {
 // KS: 32-wide k-groups (4 / 8); NP: 128-column output passes; IN_OP: 0 none, 1 GELU, 2 LayerNorm; EPI: 0 bias / residual,
 // 1 x GELU'(aux), 2 LayerNorm backward (+ residual, per-tile partials); CSR: two segmented-sum segments; LOWP: product form
 // (CSR with KS = 4: ONE segmented-sum segment - the GnBlock's neighbour sum in front of the EdgeBlock's node projection)
-template <int KS, int NP, int IN_OP, int EPI, bool CSR, int LOWP, int TG>
+// NRW: the instantiation for hidden < 128 (gfv_common.h gfv_lnq_*); the 128-wide model runs the NRW = false kernels alone
+template <int KS, int NP, int IN_OP, int EPI, bool CSR, int LOWP, int TG, bool NRW = false>
 __global__ __launch_bounds__(256, 2) void lin1s_kernel(const Lin1sArgs A, int* status) {
   constexpr int NSEG = KS / 4;   // 128-wide segments of the input
   using LY = L1sLds<KS, TG>;
@@ -204,15 +205,26 @@ __global__ __launch_bounds__(256, 2) void lin1s_kernel(const Lin1sArgs A, int* s
         sm += (v[T][4] + v[T][5]) + (v[T][6] + v[T][7]);
       }
       const float mean = row_sum(sm) * A.ln_inv_n;
-      float qq = 0.f;
+      float ssq;
+      if constexpr (!NRW) {   // the 128-wide model's arithmetic
+        float qq = 0.f;
 #pragma unroll
-      for (int T = 0; T < KS; ++T) {
-        const float d0 = v[T][0] - mean, d1 = v[T][1] - mean, d2 = v[T][2] - mean, d3 = v[T][3] - mean;
-        qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
-        const float d4 = v[T][4] - mean, d5 = v[T][5] - mean, d6 = v[T][6] - mean, d7 = v[T][7] - mean;
-        qq += (d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7);
+        for (int T = 0; T < KS; ++T) {
+          const float d0 = v[T][0] - mean, d1 = v[T][1] - mean, d2 = v[T][2] - mean, d3 = v[T][3] - mean;
+          qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+          const float d4 = v[T][4] - mean, d5 = v[T][5] - mean, d6 = v[T][6] - mean, d7 = v[T][7] - mean;
+          qq += (d4 * d4 + d5 * d5) + (d6 * d6 + d7 * d7);
+        }
+        ssq = row_sum(qq) - A.ln_npad * (mean * mean);
+      } else {   // a narrower model (gfv_common.h gfv_lnq_*)
+        gfv_lnq_t z{0.f, 0.f};
+#pragma unroll
+        for (int T = 0; T < KS; ++T)
+#pragma unroll
+          for (int e = 0; e < 8; ++e) gfv_lnq_add(z, v[T][e], mean);
+        ssq = gfv_lnq_ssq(row_sum(z.q), row_sum(z.cz), A.ln_npad, mean);
       }
-      const float rstd = rsqrtf((row_sum(qq) - A.ln_npad * (mean * mean)) * A.ln_inv_n + 1e-5f);
+      const float rstd = rsqrtf(ssq * A.ln_inv_n + 1e-5f);
 #pragma unroll
       for (int T = 0; T < KS; ++T) {
         const float4 ga0 = ld4(A.gamma + 32 * T + 4 * g), ga1 = ld4(A.gamma + 32 * T + 16 + 4 * g);
@@ -260,13 +272,24 @@ __global__ __launch_bounds__(256, 2) void lin1s_kernel(const Lin1sArgs A, int* s
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) sm += (y[nt][0] + y[nt][1]) + (y[nt][2] + y[nt][3]);
       const float mean = row_sum(sm) * A.ln_inv_n;
-      float qq = 0.f;
+      float ssq;
+      if constexpr (!NRW) {   // the 128-wide model's arithmetic
+        float qq = 0.f;
 #pragma unroll
-      for (int nt = 0; nt < 8; ++nt) {
-        const float d0 = y[nt][0] - mean, d1 = y[nt][1] - mean, d2 = y[nt][2] - mean, d3 = y[nt][3] - mean;
-        qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        for (int nt = 0; nt < 8; ++nt) {
+          const float d0 = y[nt][0] - mean, d1 = y[nt][1] - mean, d2 = y[nt][2] - mean, d3 = y[nt][3] - mean;
+          qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+        ssq = row_sum(qq) - A.ln_npad * (mean * mean);
+      } else {
+        gfv_lnq_t z{0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < 8; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gfv_lnq_add(z, y[nt][r], mean);
+        ssq = gfv_lnq_ssq(row_sum(z.q), row_sum(z.cz), A.ln_npad, mean);
       }
-      const float rstd = rsqrtf((row_sum(qq) - A.ln_npad * (mean * mean)) * A.ln_inv_n + 1e-5f);
+      const float rstd = rsqrtf(ssq * A.ln_inv_n + 1e-5f);
       if (g == 0) *reinterpret_cast<float2*>(stat + 2 * (w * 16 + j)) = make_float2(mean, rstd);
     }
   }
@@ -503,7 +526,16 @@ int gfv_internal_lin1s_try(const gfv_rowtile_args_t* a, int lowp, hipStream_t st
   if (dry) return 1;
   const int tiles = (a->M + 16 * tg - 1) / (16 * tg);
   const dim3 grid(csr ? gfv_xcd_grid(tiles) : tiles), blk(256);
-#define L1S_ONE(KS, NP, IOP, EPI, CSR, LP, TG) GFV_LAUNCH((lin1s_kernel<KS, NP, IOP, EPI, CSR, LP, TG>), grid, blk, 0, stream, B, st)
+#define L1S_ONE(KS, NP, IOP, EPI, CSR, LP, TG)                                                                     \
+  do {                                                                                                             \
+    if constexpr ((IOP) == 2 || (EPI) == 2) {   /* a LayerNorm of a model of hidden < 128: the NRW twin */         \
+      if (B.ln_npad != 0.f) {                                                                                      \
+        GFV_LAUNCH((lin1s_kernel<KS, NP, IOP, EPI, CSR, LP, TG, true>), grid, blk, 0, stream, B, st);              \
+        break;                                                                                                     \
+      }                                                                                                            \
+    }                                                                                                              \
+    GFV_LAUNCH((lin1s_kernel<KS, NP, IOP, EPI, CSR, LP, TG>), grid, blk, 0, stream, B, st);                        \
+  } while (0)
 #define L1S_FORM(LP)                                                                 \
   do {                                                                               \
     if (csr && ks == 4) L1S_ONE(4, 2, 0, 0, true, LP, 2);                            \

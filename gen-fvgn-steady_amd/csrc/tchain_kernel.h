@@ -157,32 +157,54 @@ __device__ __forceinline__ void st4_save(float* p, const float (&v)[4]) {
 
 // LayerNorm statistics of one row spread over 4 lanes x 8 x 4 registers
 // LnW: the LayerNorm width.  A model of hidden_size h < 128 runs zero-padded to 128 columns (gfv_set_hidden_size): the
-// statistics are those of the h real columns - the padded zeros add nothing to the sum, and (0 - mean)^2 each to the sum of
-// squared deviations, which is taken out again (npad = 128 - h).  h = 128: inv_n = 1/128, npad = 0 - the same arithmetic as
-// before (q - 0 * mean * mean).
-struct LnW {
+// statistics are those of the h real columns - the padded zeros, EXACTLY zero by contract (include/gfv.h), add nothing to the
+// sum; the sum of squared deviations is taken over the non-zero entries, plus mean^2 for every zero that is not one of the
+// npad = 128 - h padded ones (gfv_common.h gfv_lnq_*: no subtraction of two large numbers, no layout argument).  h = 128:
+// inv_n = 1/128, npad = 0 - the plain sum (q - 0 * mean * mean).
+// NRW: the instantiation for hidden < 128.  A launch of a 128-wide model runs the NRW = false kernels, which hold the
+// arithmetic of the 128-wide model alone (the same code, registers and occupancy as before the narrow rule existed).
+template <bool NRW>
+struct LnWT {
+  static constexpr bool narrow = NRW;
   float inv_n, npad;
 };
-__device__ __forceinline__ LnW ln_width(int cols) {
+using LnW = LnWT<false>;
+template <bool NRW>
+__device__ __forceinline__ LnWT<NRW> ln_width_t(int cols) {
   const int n = (cols > 0 && cols < 128) ? cols : 128;
-  return LnW{1.0f / (float)n, (float)(128 - n)};
+  return LnWT<NRW>{1.0f / (float)n, (float)(128 - n)};
 }
-__device__ __forceinline__ void ln_stats(const float (&v)[8][4], float& mean, float& rstd, const LnW w) {
+__device__ __forceinline__ LnW ln_width(int cols) { return ln_width_t<false>(cols); }
+__host__ __device__ inline bool ln_is_narrow(int cols) { return cols > 0 && cols < 128; }
+template <class LW>
+__device__ __forceinline__ void ln_stats(const float (&v)[8][4], float& mean, float& rstd, const LW w) {
   float s = 0.f;
 #pragma unroll
   for (int t = 0; t < 8; ++t) s += (v[t][0] + v[t][1]) + (v[t][2] + v[t][3]);
   mean = row_sum(s) * w.inv_n;
-  float q = 0.f;
+  float ssq;
+  if constexpr (!LW::narrow) {
+    float q = 0.f;
 #pragma unroll
-  for (int t = 0; t < 8; ++t) {
-    const float d0 = v[t][0] - mean, d1 = v[t][1] - mean, d2 = v[t][2] - mean, d3 = v[t][3] - mean;
-    q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    for (int t = 0; t < 8; ++t) {
+      const float d0 = v[t][0] - mean, d1 = v[t][1] - mean, d2 = v[t][2] - mean, d3 = v[t][3] - mean;
+      q += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+    }
+    ssq = row_sum(q) - w.npad * (mean * mean);
+  } else {
+    gfv_lnq_t a{0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 8; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) gfv_lnq_add(a, v[t][r], mean);
+    ssq = gfv_lnq_ssq(row_sum(a.q), row_sum(a.cz), w.npad, mean);
   }
-  rstd = rsqrtf((row_sum(q) - w.npad * (mean * mean)) * w.inv_n + 1e-5f);  // nn.LayerNorm eps (EPD.py:32)
+  rstd = rsqrtf(ssq * w.inv_n + 1e-5f);  // nn.LayerNorm eps (EPD.py:32)
 }
 
 // v <- LayerNorm(v) * gamma + beta (gamma / beta at columns 16t + 4g + r)
-__device__ __forceinline__ void ln_apply(float (&v)[8][4], const float* gamma, const float* beta, int g, const LnW w,
+template <class LW>
+__device__ __forceinline__ void ln_apply(float (&v)[8][4], const float* gamma, const float* beta, int g, const LW w,
                                          float* stats_row = nullptr) {
   float mean, rstd;
   ln_stats(v, mean, rstd, w);
@@ -200,9 +222,9 @@ __device__ __forceinline__ void ln_apply(float (&v)[8][4], const float* gamma, c
 
 // LayerNorm backward of one row: y = LN input (pre-normalisation), go = grad wrt LN output (in v, replaced by the
 // grad wrt the LN input); accumulates this lane's 32 columns of dgamma / dbeta.
-template <bool FIRST>   // FIRST: (dgam, dbet) are assigned, not added to (no zero-initialised accumulators for the first tile)
+template <bool FIRST, class LW>   // FIRST: (dgam, dbet) are assigned, not added to (no zero-initialised accumulators for the first tile)
 __device__ __forceinline__ void ln_bwd(float (&v)[8][4], const float (&y)[8][4], const float* gamma, int g,
-                                       float (&dgam)[8][4], float (&dbet)[8][4], const LnW w) {
+                                       float (&dgam)[8][4], float (&dbet)[8][4], const LW w) {
   float mean, rstd;
   ln_stats(y, mean, rstd, w);
   float s1 = 0.f, s2 = 0.f;
@@ -264,8 +286,9 @@ __device__ __forceinline__ void ln_park(float (&dgam)[8][4], float (&dbet)[8][4]
 // dy * xhat and its 32 dy go through the row fold and into LDS four at a time - holding all 64 through the second half of
 // ln_bwd and handing them to ln_park afterwards keeps 64 more registers alive in the most register-hungry phase of the
 // LayerNorm-backward instantiation.
+template <class LW>
 __device__ __forceinline__ void ln_bwd_park(float (&v)[8][4], const float (&y)[8][4], const float* gamma, int g, float* red,
-                                            int wave, int li, const LnW w) {
+                                            int wave, int li, const LW w) {
   float mean, rstd;
   ln_stats(y, mean, rstd, w);
   float s1 = 0.f, s2 = 0.f;
@@ -417,10 +440,10 @@ __device__ __forceinline__ void to_halves(const float (&v)[8][4], float sc, gfv_
 }
 
 // ---- input segment -> activation registers (gather / concat piece / prologue element ops) -------------------------
-template <int T, int LNM, bool RAG, bool CSR>
+template <int T, int LNM, bool RAG, bool CSR, class LW>
 __device__ __forceinline__ void load_segment(const gfv_rowtile_args_t& A, int si, int rowbase, int g, const float* gam,
                                              const float* bet, float (&act)[T][8][4], float (&dgam)[8][4],
-                                             float (&dbet)[8][4], int in_op, float* red, int wave, int li, const LnW lnw) {
+                                             float (&dbet)[8][4], int in_op, float* red, int wave, int li, const LW lnw) {
   const gfv_seg_t& s = A.seg[si];
   const int nt_valid = s.width >> 4;
   const bool first = (si == 0);
@@ -574,7 +597,7 @@ __device__ __forceinline__ void load_segment(const gfv_rowtile_args_t& A, int si
 // handful of the model's launches are.  With the ops known at compile time the epilogues have no branches to merge:
 // hipcc joins the arms of a run-time `switch (op)` over a 32-register activation array with 100 - 150 register moves per
 // layer (a tenth of the kernel's VALU instructions).
-template <int T, int LNM, bool RAG, bool H, int NW = 4, bool CSR = false, int IOP = 0, bool BF = false>
+template <int T, int LNM, bool RAG, bool H, int NW = 4, bool CSR = false, int IOP = 0, bool BF = false, bool NRW = false>
 #ifndef GFV_CHAIN_WAVES   // waves per SIMD the register allocation aims at (a translation unit may set its own)
 #define GFV_CHAIN_WAVES(H, LNM, RAG) 2
 #endif
@@ -607,7 +630,7 @@ __global__ __launch_bounds__(64 * NW, GFV_CHAIN_WAVES(H, LNM, RAG)) void tchain_
   float sx = 1.f;                                            // H: this row's current power-of-two scale
   const float ws = H ? gfv_pow2_scale(*A.wmax) : 1.f;        // H: the images' weight scale
   const bool lowp = H && A.product_form != 0;
-  const LnW lnw = ln_width(A.hidden);                          // LayerNorm width (0 / 128: every column)                       // H: reduced-precision form (hi x hi products only)
+  const LnWT<NRW> lnw = ln_width_t<NRW>(A.hidden);                          // LayerNorm width (0 / 128: every column)                       // H: reduced-precision form (hi x hi products only)
 
   // gather rows of the factored first-layer addend: index round trip issued first thing, used in the first epilogue
   const float* pad_s[T];
@@ -902,3 +925,13 @@ __global__ __launch_bounds__(64 * NW, GFV_CHAIN_WAVES(H, LNM, RAG)) void tchain_
 
 }  // namespace
 
+
+// Every launch of the chain: `args` points at the launch's gfv_rowtile_args_t, whose `hidden` the launcher has filled in.  A
+// model of hidden < 128 runs the NRW twin of the same instantiation (ln_stats); the 128-wide model's kernels are untouched by it.
+#define TCHAIN_LAUNCH(T, LNM, RAG, H, NW, CSR, IOP, BF, grid, blk, stream, args)                                          \
+  do {                                                                                                                    \
+    if (ln_is_narrow((args)->hidden))                                                                                     \
+      GFV_LAUNCH((tchain_kernel<T, LNM, RAG, H, NW, CSR, IOP, BF, true>), grid, blk, 0, stream, *(args));                 \
+    else                                                                                                                  \
+      GFV_LAUNCH((tchain_kernel<T, LNM, RAG, H, NW, CSR, IOP, BF, false>), grid, blk, 0, stream, *(args));                \
+  } while (0)

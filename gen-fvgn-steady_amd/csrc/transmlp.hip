@@ -108,7 +108,8 @@ struct TmFwdArgs {
 // the rows of fx1 the last residual adds are parked in the lane's own elements of `out`, which the same lane reads back and
 // overwrites at the end (the kernel sits at its 256-register budget: the 32 residual values per lane do not fit beside the 64
 // fragment registers of the 256-deep product).  The same products, sums and scales in the same order: bit-identical `out`.
-template <int LOWP, bool SAVE>
+// NRW: the instantiation for hidden < 128 (gfv_common.h gfv_lnq_*); the 128-wide model runs the NRW = false kernels alone
+template <int LOWP, bool SAVE, bool NRW = false>
 __global__ __launch_bounds__(512, 2) void trans_mlp_fwd_kernel(const TmFwdArgs A, int* status) {
   constexpr bool BF = LOWP == 2;
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
@@ -150,13 +151,24 @@ __global__ __launch_bounds__(512, 2) void trans_mlp_fwd_kernel(const TmFwdArgs A
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) sm += (h[nt][0] + h[nt][1]) + (h[nt][2] + h[nt][3]);
       const float mean = row_sum(sm) * A.ln_inv_n;
-      float qq = 0.f;
+      float ssq;
+      if constexpr (!NRW) {   // the 128-wide model's arithmetic
+        float qq = 0.f;
 #pragma unroll
-      for (int nt = 0; nt < 8; ++nt) {
-        const float d0 = h[nt][0] - mean, d1 = h[nt][1] - mean, d2 = h[nt][2] - mean, d3 = h[nt][3] - mean;
-        qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        for (int nt = 0; nt < 8; ++nt) {
+          const float d0 = h[nt][0] - mean, d1 = h[nt][1] - mean, d2 = h[nt][2] - mean, d3 = h[nt][3] - mean;
+          qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+        ssq = row_sum(qq) - A.ln_npad * (mean * mean);
+      } else {   // a narrower model (gfv_common.h gfv_lnq_*)
+        gfv_lnq_t z{0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < 8; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gfv_lnq_add(z, h[nt][r], mean);
+        ssq = gfv_lnq_ssq(row_sum(z.q), row_sum(z.cz), A.ln_npad, mean);
       }
-      const float rstd = rsqrtf((row_sum(qq) - A.ln_npad * (mean * mean)) * A.ln_inv_n + 1e-5f);
+      const float rstd = rsqrtf(ssq * A.ln_inv_n + 1e-5f);
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) {
         const float4 ga = ld4(A.gamma + 16 * nt + 4 * g), be = ld4(A.beta + 16 * nt + 4 * g);
@@ -230,7 +242,7 @@ struct TmBwdArgs {
   float ln_inv_n, ln_npad;
 };
 
-template <int LOWP>
+template <int LOWP, bool NRW = false>
 __global__ __launch_bounds__(512, 2) void trans_mlp_bwd_kernel(const TmBwdArgs A, int* status) {
   constexpr bool BF = LOWP == 2;
   extern __shared__ __attribute__((aligned(16))) char lds_raw[];
@@ -321,13 +333,24 @@ __global__ __launch_bounds__(512, 2) void trans_mlp_bwd_kernel(const TmBwdArgs A
 #pragma unroll
       for (int nt = 0; nt < 8; ++nt) sm += (y[nt][0] + y[nt][1]) + (y[nt][2] + y[nt][3]);
       const float mean = row_sum(sm) * A.ln_inv_n;
-      float qq = 0.f;
+      float ssq;
+      if constexpr (!NRW) {   // the 128-wide model's arithmetic
+        float qq = 0.f;
 #pragma unroll
-      for (int nt = 0; nt < 8; ++nt) {
-        const float d0 = y[nt][0] - mean, d1 = y[nt][1] - mean, d2 = y[nt][2] - mean, d3 = y[nt][3] - mean;
-        qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        for (int nt = 0; nt < 8; ++nt) {
+          const float d0 = y[nt][0] - mean, d1 = y[nt][1] - mean, d2 = y[nt][2] - mean, d3 = y[nt][3] - mean;
+          qq += (d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3);
+        }
+        ssq = row_sum(qq) - A.ln_npad * (mean * mean);
+      } else {
+        gfv_lnq_t z{0.f, 0.f};
+#pragma unroll
+        for (int nt = 0; nt < 8; ++nt)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) gfv_lnq_add(z, y[nt][r], mean);
+        ssq = gfv_lnq_ssq(row_sum(z.q), row_sum(z.cz), A.ln_npad, mean);
       }
-      const float rstd = rsqrtf((row_sum(qq) - A.ln_npad * (mean * mean)) * A.ln_inv_n + 1e-5f);
+      const float rstd = rsqrtf(ssq * A.ln_inv_n + 1e-5f);
       const float livef = live ? 1.0f : 0.0f;   // rows past M must not reach the (dgamma, dbeta) sums
       float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -452,6 +475,12 @@ extern "C" int gfv_trans_mlp_fwd(const gfv_trans_mlp_t* a, void* stream) {
 #define TM_F(LP, SV)                                                                                       \
   do {                                                                                                    \
     static std::atomic<unsigned long long> done{0};                                                       \
+    static std::atomic<unsigned long long> done_n{0};                                                     \
+    if (B.ln_npad != 0.f) {   /* a model of hidden < 128: the NRW twin */                                 \
+      if (!tm_dyn_lds(reinterpret_cast<const void*>(&trans_mlp_fwd_kernel<LP, SV, true>), done_n)) return GFV_ERR_LAUNCH; \
+      GFV_LAUNCH((trans_mlp_fwd_kernel<LP, SV, true>), grid, blk, 131072, (hipStream_t)stream, B, st);    \
+      break;                                                                                              \
+    }                                                                                                     \
     if (!tm_dyn_lds(reinterpret_cast<const void*>(&trans_mlp_fwd_kernel<LP, SV>), done)) return GFV_ERR_LAUNCH; \
     GFV_LAUNCH((trans_mlp_fwd_kernel<LP, SV>), grid, blk, 131072, (hipStream_t)stream, B, st);               \
   } while (0)
@@ -496,6 +525,12 @@ extern "C" int gfv_trans_mlp_bwd(const gfv_trans_mlp_bwd_t* a, void* stream) {
 #define TM_B(LP)                                                                                          \
   do {                                                                                                    \
     static std::atomic<unsigned long long> done{0};                                                       \
+    static std::atomic<unsigned long long> done_n{0};                                                     \
+    if (B.ln_npad != 0.f) {   /* a model of hidden < 128: the NRW twin */                                 \
+      if (!tm_dyn_lds(reinterpret_cast<const void*>(&trans_mlp_bwd_kernel<LP, true>), done_n)) return GFV_ERR_LAUNCH; \
+      GFV_LAUNCH((trans_mlp_bwd_kernel<LP, true>), grid, blk, 131072, (hipStream_t)stream, B, st);        \
+      break;                                                                                              \
+    }                                                                                                     \
     if (!tm_dyn_lds(reinterpret_cast<const void*>(&trans_mlp_bwd_kernel<LP>), done)) return GFV_ERR_LAUNCH; \
     GFV_LAUNCH((trans_mlp_bwd_kernel<LP>), grid, blk, 131072, (hipStream_t)stream, B, st);               \
   } while (0)

@@ -286,7 +286,12 @@ int gfv_set_f16split_thread(int32_t on);
  * 128 columns (the host side pads its parameters: FVMmodel/padding.py) and differs in two places only - LayerNorm takes its
  * statistics over the h real columns, and the slice attention scales by (h / 8) ** -0.5.  Thread-local host state read by
  * the launchers: set it before the launches of a model (gfv.engine.Engine does, on every forward and backward); a chain
- * launch may name its own (gfv_rowtile_args_t.hidden). */
+ * launch may name its own (gfv_rowtile_args_t.hidden).
+ * PRECONDITION at h < 128: the padded columns of every LayerNorm input are EXACTLY zero (zero-padded weights, biases, gamma and
+ * beta keep them so).  No launch is told where the h real columns sit (node latents 0 .. h - 1, the halves of an edge latent
+ * at 0 and 64): the statistics are mean = sum_128 / h and sum_sq = sum over the NON-ZERO entries of (x - mean)^2 + (number of
+ * zero entries - (128 - h)) mean^2 - a zero beyond the 128 - h padded ones is a real column that deviates by -mean.  A non-zero
+ * value in a padded column is counted as a real one.  h = 128 runs kernels of its own, which hold the plain sum only. */
 int gfv_hidden_size(void);
 int gfv_set_hidden_size(int32_t h);
 int gfv_weight_absmax(const gfv_wimg_desc_t* descs_dev, int32_t n_desc, float* wmax, void* stream);

@@ -128,6 +128,7 @@ class Case:
     flat: bool = False         # flat O(1) operands: forms 2 / 3 must be FORM_DISTANCE from the unrounded product
     floor: bool = False        # unscaled small activations: the split form gets the format's floor
     o1_cols: torch.Tensor = None
+    ln_offset: float = 0.0     # a_op 2: |mean| / std of the LayerNorm input rows (judge)
 
     @property
     def narrow(self):
@@ -382,15 +383,16 @@ Check = collections.namedtuple("Check", "name kind value ok")
 
 
 class Checks(list):
-    def summed(self, name, got, ref, mag, floor=None):
-        """|got - ref| <= 2e-6 * mag (+ floor) on every entry - an entry without terms must be zero -, and ref must not vanish
+    def summed(self, name, got, ref, mag, floor=None, widen=1.0):
+        """(the recorded value is divided by `widen` >= 1: judge(), cases with a LayerNorm row offset)
+        |got - ref| <= 2e-6 * mag (+ floor) on every entry - an entry without terms must be zero -, and ref must not vanish
         next to mag on at least half of the entries that have terms (an all-zero output cannot pass; the dead columns of a
         LayerNorm over fewer than 128 real columns, or a zero column, have none)."""
         got, ref = got.double(), ref.double()
         err = (got - ref).abs()
         if floor is not None:
             err = (err - floor).clamp(min=0)
-        v = float(torch.where(mag > 0, err / mag.clamp(min=1e-300), torch.where(err > 0, float("inf"), 0.0).double()).max())
+        v = float(torch.where(mag > 0, err / mag.clamp(min=1e-300), torch.where(err > 0, float("inf"), 0.0).double()).max()) / widen
         self.append(Check(name, "sum", v, v < LIMITS["sum"][0]))
         frac = float(((ref.abs() >= 1e-3 * mag) & (mag > 0)).double().sum() / max(int((mag > 0).sum()), 1)) if mag.numel() else 1.0
         self.append(Check(name + ": entries with |ref| >= 1e-3 sum|terms|", "atleast", frac, frac >= 0.5))
@@ -429,10 +431,29 @@ def reference(case):
     return _REF[key]
 
 
+_E32 = {}
+
+
+def torch32_figure(case):
+    """The largest |float32 torch - float64| / sum|terms| over the entries of a case's dW and db (computed once)."""
+    key = (case.name, case.M)
+    if key not in _E32:
+        v = 0.0
+        for g, r in zip(Torch32().run(case), reference(case)):
+            for a, b, m in ((g.dW, r.dW, r.magW), (g.db, r.db, r.magb)):
+                if a is not None and bool((m > 0).any()):
+                    v = max(v, float(((a.double() - b.double()).abs()[m > 0] / m[m > 0]).max()))
+        _E32[key] = v
+    return _E32[key]
+
+
 def judge(case, got, ck=None):
-    """The checks of one case on a backend's results `got` ([Result] per tile)."""
+    """The checks of one case on a backend's results `got` ([Result] per tile).  A case whose LayerNorm input rows carry an offset
+    (ln_offset: their mean is that many standard deviations from zero) is held to max(2e-6, 4 e32) of sum|terms|, e32 the figure of
+    the float32 torch evaluation of the same case - tests/ln_width.py's rule: the reference's arithmetic keeps a quarter."""
     ck = Checks() if ck is None else ck
     ref = reference(case)
+    widen = max(1.0, 4.0 * torch32_figure(case) / LIMITS["sum"][0]) if case.ln_offset else 1.0
     emu = Emu(case.form).run(case) if case.form in (2, 3) and not case.exact else None
     for i, (t, g, r) in enumerate(zip(case.tiles, got, ref)):
         tag = f"{case.name} M {case.M} form {case.form} tile {i}"
@@ -442,7 +463,7 @@ def judge(case, got, ck=None):
                 ck.equal(tag + " db", g.db, r.db)
             continue
         if g.db is not None:
-            ck.summed(tag + " db", g.db, r.db, r.magb)
+            ck.summed(tag + " db", g.db, r.db, r.magb, widen=widen)
         if not case.floor and not t.colscale and case.M > 0:
             # (reference only) the fp16 floor of unscaled activations stays below a quarter of the limit where it is not granted
             has = r.magW > 0
@@ -450,7 +471,7 @@ def judge(case, got, ck=None):
             ck.cond(tag + ": fp16 floor of the activations / sum|terms|", ratio, ratio <= LIMITS["sum"][1])
         if emu is None or case.narrow:
             floor = FLOOR_Q * r.magb[:, None].expand_as(r.dW) if (case.floor and case.form == 1 and not t.colscale) else None
-            ck.summed(tag + " dW", g.dW, r.dW, r.magW, floor=floor)
+            ck.summed(tag + " dW", g.dW, r.dW, r.magW, floor=floor, widen=widen)
             if floor is not None:    # (informative) how far the small columns are from the float64 product, and how much of the bound is used
                 err = (g.dW.double() - r.dW).abs()
                 ck.append(Check(tag + " dW / sum|terms| with no floor granted", "raw", float((err / r.magW).max()), True))
@@ -515,9 +536,12 @@ def _index(g, M, R, A):
 
 
 def linear_case(name, M, form=0, n_out=128, ldg=128, g_offset=0, segs=((128, 128, 0),), idx=None, in_add=False, a_op=0,
-                hidden=128, layout="node", colscale=False, exact=False, flat=False, g_rows=None, a_cols=None, a_rows=None, zero_col=None):
+                hidden=128, layout="node", colscale=False, exact=False, flat=False, g_rows=None, a_cols=None, a_rows=None, zero_col=None,
+                ln_offset=0.0):
     """One G, one to three segments (width, ld, column offset).  idx: None, "more" (a source of M + 37 rows) or "fewer"
-    (of about M / 2).  g_rows / a_cols / a_rows: factors per row of G / per column / per source row of the first segment."""
+    (of about M / 2).  g_rows / a_cols / a_rows: factors per row of G / per column / per source row of the first segment.
+    ln_offset (a_op 2): added to the real columns of the LayerNorm input rows - their |mean| / std (tests/ln_width.py) - with an
+    exact zero in the first real column of every 7th source row."""
     g = _seed(name, M)
     G = _values(g, (max(M, 1), ldg), exact, 2)
     if g_rows is not None:
@@ -538,6 +562,11 @@ def linear_case(name, M, form=0, n_out=128, ldg=128, g_offset=0, segs=((128, 128
             A[:, col:col + width][:, ~real] = 0.0
             if add is not None:
                 add[:, :width][:, ~real] = 0.0
+            if ln_offset:
+                A[:, col:col + width][:, real] += ln_offset
+                A[::7, col] = 0.0
+                if add is not None:
+                    add[::7, 0] = 0.0
         if a_cols is not None and i == 0:
             A[:, col:col + width] *= a_cols
         if a_rows is not None and i == 0:
@@ -550,7 +579,7 @@ def linear_case(name, M, form=0, n_out=128, ldg=128, g_offset=0, segs=((128, 128
             t.gamma = torch.where(real, 1 + 0.2 * torch.randn(128, generator=g), torch.zeros(128))
             t.beta = torch.where(real, 0.2 * torch.randn(128, generator=g), torch.zeros(128))
         tiles.append(t)
-    c = Case(name, M, tiles, form=form, hidden=hidden, layout=layout, exact=exact, flat=flat)
+    c = Case(name, M, tiles, form=form, hidden=hidden, layout=layout, exact=exact, flat=flat, ln_offset=ln_offset)
     c.block_floats = lay_out(tiles, True)
     return c
 
@@ -589,6 +618,24 @@ def onload_cases(form, M):
     yield linear_case("LayerNorm h 64 node, n_out 64", M, form, n_out=64, ldg=64, a_op=2, hidden=64)
     yield linear_case("LayerNorm h 64 node", M, form, a_op=2, hidden=64)
     yield linear_case("LayerNorm h 32 edge", M, form, a_op=2, hidden=32, layout="edge")
+
+
+LN_OFFSETS = (8, 32)      # tests/ln_width.py OFFSETS; 0: onload_cases, and below for the widths those do not hold
+
+
+def ln_offset_cases(form, M):
+    """LayerNorm on load of rows whose mean is 8 / 32 standard deviations from zero, at every width and in both layouts, exact
+    zeros inside real columns: a rule that subtracts (128 - h) mean^2 from a sum over all 128 columns loses
+    (mean / std)^2 (128 - h) / h ulps of the variance here (csrc/gfv_common.h gfv_lnq_*)."""
+    # (h = 16: a row of 16 samples can have a standard deviation below the 0.5 that onload_cases promise)
+    yield linear_case("LayerNorm h 16 node offset 0", M, form, a_op=2, hidden=16)
+    yield linear_case("LayerNorm h 16 edge offset 0", M, form, a_op=2, hidden=16, layout="edge")
+    yield linear_case("LayerNorm h 112 edge offset 0", M, form, a_op=2, hidden=112, layout="edge")
+    for off in LN_OFFSETS:
+        for h, lay in ((16, "node"), (16, "edge"), (32, "edge"), (64, "node"), (112, "edge"), (128, "node")):
+            yield linear_case(f"LayerNorm h {h} {lay} offset {off}", M, form, a_op=2, hidden=h, layout=lay, ln_offset=float(off))
+        yield linear_case(f"LayerNorm h 32 node offset {off} + in_add + idx", M, form, a_op=2, hidden=32, in_add=True, idx="fewer",
+                          ln_offset=float(off))
 
 
 def decades(M):

@@ -12,6 +12,8 @@ quarter of each), with the worst figure measured on the MI355X per case family, 
     row geometry                         2.6e-7 / 5.2e-7 / 1.2e-7 / 8.4e-8
     width geometry, M = 97               2.0e-7 / 1.1e-7 / 8.0e-8 / 8.0e-8        M = 333   8.7e-8 / 6.7e-8 / 4.3e-8 / 4.0e-8
     on-load operations, M = 97           2.4e-7 / 1.5e-7 / 6.7e-8 / 5.4e-8        M = 1100  5.7e-8 / 4.0e-8 / 2.3e-8 / 1.7e-8
+    LayerNorm of rows 8 / 32 std from zero, hidden 16 .. 128 (in units of max(2e-6, 4 e32), D.judge), M = 97
+                                         7.5e-7 / 7.3e-7 / 3.5e-8 / 3.5e-8        M = 1100  3.6e-7 / 3.5e-7 / 1.4e-8 / 1.4e-8
     scales                               3.6e-7 / 4.5e-7 / 4.8e-7 / 2.7e-7
     group scales, M = 33 / 97 / 3001     2.3e-7 / 5.0e-7 / 2.3e-7 / 2.3e-7 (the largest of the three)
     six tiles, M = 97                    2.1e-7 / 1.4e-7 / 6.4e-8 / 6.3e-8        M = 3019  3.5e-8 / 2.7e-8 / 1.4e-8 / 1.2e-8
@@ -142,6 +144,13 @@ def test_on_load_operations(dev, form, M):
     """in_add, in_add + gather + GELU, LayerNorm on load at hidden 128, 64 (node layout) and 32 (edge layout: halves at columns
     0 and 64) with zero dead columns and gamma = beta = 0 there - the reference normalises over the real columns only."""
     _judge(dev, D.onload_cases(form, M), f"on-load form {form} M {M}")
+
+
+@pytest.mark.parametrize("M", [97, 1100])
+def test_on_load_layernorm_of_rows_far_from_zero(dev, form, M):
+    """LayerNorm on load at hidden 16 / 32 / 64 / 112 / 128 of rows whose mean is 8 / 32 standard deviations from zero, with exact
+    zeros inside real columns, and at hidden 16 / 112 without an offset (D.ln_offset_cases): the limits of every on-load case."""
+    _judge(dev, D.ln_offset_cases(form, M), f"on-load LayerNorm offsets form {form} M {M}")
 
 
 def test_scales(dev, form):
