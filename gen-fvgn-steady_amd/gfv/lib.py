@@ -118,6 +118,8 @@ TIME_BC_RECORD, TIME_BC_CTL, TIME_BC_HIST, TIME_BC_TABLE_MAX = 8, 4, 3, 1024
 TIME_BC_NONE, TIME_BC_CONST, TIME_BC_RAMP_LINEAR, TIME_BC_RAMP_SMOOTH, TIME_BC_SINE, TIME_BC_TABLE, TIME_BC_TABLE_PERIODIC = range(7)
 # GFV_TIME_SCHEME_* of include/gfv.h: words of the record, the schemes of gfv_time_scheme_update
 TIME_SCHEME_RECORD, TIME_SCHEME_BDF1, TIME_SCHEME_BDF2 = 4, 1, 2
+# GFV_STEP_CONTROL_* of include/gfv.h: words of the control record, floats of the parameters, rows of the per-graph state
+STEP_CONTROL_RECORD, STEP_CONTROL_PARAMS, STEP_CONTROL_STATE = 4, 8, 4
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -301,6 +303,8 @@ _SIGNATURES = {
     "gfv_time_bc_update": (C.c_int, [C.c_void_p] * 7 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4 + [C.c_int32] + [C.c_void_p] * 3
                            + [C.c_int32] * 3 + [C.c_void_p]),
     "gfv_time_scheme_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "gfv_step_control_rate": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]),
+    "gfv_step_control_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -60,6 +60,14 @@ starts at second order).  Second order in time needs `integrator="implicit"`.  I
 they found before and write the same bits again.  With it `state_dict()` carries the previous level's velocity
 (`gfv_time_scheme`: one synchronisation) and `load_state_dict()` installs it, so a march that resumes in a new object on the
 carried-over field continues at second order.  `time_scheme=None` (the default) issues no new launch and allocates nothing.
+
+`time_scheme=TimeScheme("bdf2", adapt=StepControl(courant=2.0, ...))`: the step of every level is sized on the
+device to a Courant-number target - two launches behind the march launch in place of the one: the Courant rate of the level's
+field (a maximum over its cells) with the controller, then the baseline with the variable-step coefficients.  The host cannot do
+this: it does not know which step ends a level.  Inner iterations and held steps write the same bits again, the step, the time
+and the history row included; `ms.time_scheme.read()` shows the step, the time and the Courant number, `step_history()` the last
+levels'.  `gfv_time_scheme` of `state_dict()` then also carries the last step and the time, and a resumed march continues with
+them.  Refused together with `time_bc=` (it forms t = level * plan.dt) and `field_stats=` (its means are unweighted in time).
 """
 from __future__ import annotations
 
@@ -75,7 +83,7 @@ from . import lib as L
 from . import timebc as TB
 from .fieldstats import FieldStats
 from .schedule import Plateau
-from .timescheme import check_owner as check_time_scheme
+from .timescheme import check_adapt_owner, check_owner as check_time_scheme
 from .trainer import TrainStep
 
 # words of the march record (include/gfv.h gfv_march_advance)
@@ -156,6 +164,7 @@ class MarchStep(TrainStep):
                  use_graph="list", field_stats=None, time_bc=None, time_scheme=None, **trainstep_kwargs):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
+        check_adapt_owner("MarchStep", time_scheme, time_bc, field_stats)
         if field_stats is not None and not isinstance(field_stats, FieldStats):
             raise ValueError(f"MarchStep: field_stats must be a gfv.fieldstats.FieldStats or None, got {field_stats!r}")
         if field_stats is not None:
@@ -386,8 +395,8 @@ class MarchStep(TrainStep):
     def state_dict(self):
         """TrainStep's; with `time_bc` also the time the boundary data have reached: `gfv_time_bc` = {"clock": levels completed,
         this object's clock offset included} (one synchronisation); with `time_scheme` also `gfv_time_scheme` = {"scheme",
-        "has_previous", "previous" [N, 2] CPU tensor}: the velocity of level count - 1 (one synchronisation).  The march record
-        itself is not part of it."""
+        "has_previous", "previous" [N, 2] CPU tensor}: the velocity of level count - 1 (one synchronisation), and with an adaptive
+        scheme its "dt_last" [B] and "time" [B].  The march record itself is not part of it."""
         sd = super().state_dict()
         if self.time_scheme is not None:
             sd["gfv_time_scheme"] = self.time_scheme.state_dict()

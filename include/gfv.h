@@ -1176,6 +1176,55 @@ int gfv_time_scheme_update(const float* x_backup, const int32_t* batch, const fl
                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Adaptive time step of a march (gfv/timescheme.py StepControl): the step sized to a Courant-number target and the
+ * variable-step form of BDF2.  TWO launches in place of gfv_time_scheme_update, behind whatever has advanced the field, on the
+ * same stream: gfv_step_control_rate, then gfv_step_control_rows.  `x_backup`, `batch`, `uvp_dim`, `dt`, `clock`, `rec`, `ring`,
+ * `ustar` and `dt_eff` are gfv_time_scheme_update's.  New, everything per graph b:
+ *   crow int32 [C + 1], knode int32 [crow[C]], kS float [crow[C], 2] (8-byte aligned), area float [C], cbatch int32 [C] ascending:
+ *              the (cell, node) incidences of the plan and their face vectors
+ *   crec       GFV_STEP_CONTROL_RECORD int32 words: [0] tbase (host): the last clock whose step and time are the host's (dt0, time0);
+ *              [1] the arrival counter (zero between launches);  [2], [3] zero
+ *   par        GFV_STEP_CONTROL_PARAMS floats (host): courant, grow, shrink, min_factor, max_factor, 0, 0, 0
+ *   dt0 float [B], time0 double [B] (host): the step that produced field tbase and its time
+ *   rate       uint32 [2, B]: the bits of the Courant rate, one slot per clock parity; both zero before the first launch
+ *   dts        float [2, B]: dts[c & 1] the step that produced field c;   times  double [2, B]: times[c & 1] the time of field c
+ *   state      float [GFV_STEP_CONTROL_STATE, B]: rows dt_next, omega, courant, rate - of the clock the last launch found
+ *   hist_clock int32 [keep], hist float [keep, 2, B] (dt_next, courant), hist_time double [keep, B]: row c % keep
+ * The rule, with c = *clock, rec, crec[0] and par AS THE LAUNCH FINDS THEM; every operation ONE IEEE float operation in the order
+ * written, nothing contracted, sums over k ascending from +0:
+ *   cell j of graph b = cbatch[j], k in crow[j] .. crow[j + 1] - 1, n their number (n = 0: rate_j = 0):
+ *     sx = sum_k x_backup[knode[k], 0] / uvp_dim[3 b];  sy likewise with column 1 and uvp_dim[3 b + 1];  mx = sx / n;  my = sy / n
+ *     rate_j = (sum_k |mx * kS[k, 0] + my * kS[k, 1]|) / (2 * area[j]);  anything not > 0 (a NaN too) counts as +0
+ *   rate[c & 1][b] = max(rate[c & 1][b], max_j rate_j) by integer maxima of the bits (exact in any order);  rate[(c & 1) ^ 1][b] = 0
+ *   then, by the workgroup that arrives last, with first = (c <= tbase), active = (scheme == GFV_TIME_SCHEME_BDF2 && c > base):
+ *     dt_last = first ? dt0[b] : dts[c & 1][b];   Co = rate * dt_last
+ *     fac = Co > 0 ? courant / Co : grow;   fac = min(max(fac, shrink), grow)
+ *     dt_next = dt_last * fac;   dt_next = min(max(dt_next, min_factor * dt[b]), max_factor * dt[b]);   omega = dt_next / dt_last
+ *     dt_eff[b] = active ? dt_next / ((1 + 2 * omega) / (1 + omega)) : dt_next
+ *     time = first ? time0[b] : times[(c & 1) ^ 1][b] + (double)dt_last          (one double addition)
+ *     dts[(c + 1) & 1][b] = dt_next;  times[c & 1][b] = time;  state and the history row c % keep as above;  hist_clock = c
+ *   gfv_step_control_rows, row i of graph b, channel k, cur and prev as in gfv_time_scheme_update:
+ *     active:      q = (1 + 2 * omega) / (omega * omega);  s = cur + (cur - prev) / q;  ustar[i][k] = s / uvp_dim[3 b + k]
+ *     otherwise:   ustar[i][k] = cur / uvp_dim[3 b + k];      either way ring[c & 1][i][k] = cur
+ * The weights omega^2 / (1 + 2 omega) and (1 + omega) / (1 + 2 omega) are applied as divisions by their reciprocals: at omega = 1
+ * the divisors are exactly 3 and 1.5, and the pair writes the bits of gfv_time_scheme_update.  The pair reads no word it writes (the rate slot it adds to takes
+ * a maximum: adding the same cells again leaves it), so a pair that finds the clock it found before writes the same bits
+ * everywhere, the history row included.  `dt` is never written.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, C, B, N or keep < 1, an x_backup that is not 16-byte aligned, or a kS, time0,
+ * times, hist_time, ring or ustar that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_STEP_CONTROL_RECORD 4
+#define GFV_STEP_CONTROL_PARAMS 8
+#define GFV_STEP_CONTROL_STATE 4
+int gfv_step_control_rate(const float* x_backup, const float* uvp_dim, const float* dt, const int32_t* crow, const int32_t* knode,
+                          const float* kS, const float* area, const int32_t* cbatch, int32_t C, int32_t B, const int32_t* clock,
+                          const int32_t* rec, int32_t* crec, const float* par, const float* dt0, const double* time0,
+                          uint32_t* rate, float* dts, double* times, float* state, float* dt_eff, int32_t* hist_clock, float* hist,
+                          double* hist_time, int32_t keep, void* stream);
+int gfv_step_control_rows(const float* x_backup, const int32_t* batch, const float* uvp_dim, int32_t N, int32_t B,
+                          const int32_t* clock, const int32_t* rec, const float* state, float* ring, float* ustar, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
  * at pre_train_Adam.py:203 and solve_with_grad_GPU.py:197, and torch.optim.lr_scheduler.ReduceLROnPlateau).  ONE launch of one
  * wave recomputes the rate from a device record and writes it where the Adam launches read it:
