@@ -120,6 +120,8 @@ TIME_BC_NONE, TIME_BC_CONST, TIME_BC_RAMP_LINEAR, TIME_BC_RAMP_SMOOTH, TIME_BC_S
 TIME_SCHEME_RECORD, TIME_SCHEME_BDF1, TIME_SCHEME_BDF2 = 4, 1, 2
 # GFV_STEP_CONTROL_* of include/gfv.h: words of the control record, floats of the parameters, rows of the per-graph state
 STEP_CONTROL_RECORD, STEP_CONTROL_PARAMS, STEP_CONTROL_STATE = 4, 8, 4
+# GFV_WALL_FORCE_* of include/gfv.h: words of the record (gfv_field_stats_update's), sums per graph, faces per chunk at most
+WALL_FORCE_RECORD, WALL_FORCE_SUMS, WALL_FORCE_CHUNK = 8, 6, 64
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -305,6 +307,9 @@ _SIGNATURES = {
     "gfv_time_scheme_update": (C.c_int, [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     "gfv_step_control_rate": (C.c_int, [C.c_void_p] * 8 + [C.c_int32, C.c_int32] + [C.c_void_p] * 14 + [C.c_int32, C.c_void_p]),
     "gfv_step_control_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "gfv_wall_force_grad": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4),
+    "gfv_wall_force_sum": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p] * 7
+                           + [C.c_int32, C.c_void_p]),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -45,6 +45,13 @@ per completed level (the field level 0 leaves has clock 1), whatever its inner c
 steps, sample nothing.  `ms.field_stats.read()` reads them; `stats()` keeps its meaning (the march record).  Not part of
 `state_dict()`.  `field_stats=None` (the default) issues no new launch and allocates nothing.
 
+`wall_forces=WallForces(faces=, box=, origin=, start=, stride=, stop=, keep=)` (gfv/wallforce.py): two more launches behind
+the march launch, where `field_stats` launches, sum the pressure and the viscous force on the selected wall faces, and their moments,
+per graph, for every COMPLETED level - one row of a device ring per level, whatever its inner count; held steps add nothing.
+`ms.wall_forces.read()` reads them.  Allowed beside `field_stats`, `time_bc` and `time_scheme` (`StepControl` included: the time of a
+sample is joined through its clock with `step_history()`); refused for graphs of a DevicePool.  Not part of `state_dict()`.
+`wall_forces=None` (the default) issues no new launch and allocates nothing.
+
 `time_bc=TimeBC(velocity=, source=, nodes=)` (gfv/timebc.py): one more launch behind the march launch rewrites the
 Dirichlet velocity targets and the source coefficient for the level about to be computed (level count + 1), from per-graph waveform
 records on the device.  The host cannot do this: only the device knows which step starts a new level.  Inner iterations and held
@@ -81,6 +88,7 @@ import torch
 
 from . import lib as L
 from . import timebc as TB
+from . import wallforce as WF
 from .fieldstats import FieldStats
 from .schedule import Plateau
 from .timescheme import check_adapt_owner, check_owner as check_time_scheme
@@ -161,7 +169,7 @@ def decode_history(words, B):
 
 class MarchStep(TrainStep):
     def __init__(self, model, graphs, *, max_inner=20, min_inner=1, tol=1e-2, abs_tol=None, max_levels=1000, keep=0,
-                 use_graph="list", field_stats=None, time_bc=None, time_scheme=None, **trainstep_kwargs):
+                 use_graph="list", field_stats=None, time_bc=None, time_scheme=None, wall_forces=None, **trainstep_kwargs):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
         check_adapt_owner("MarchStep", time_scheme, time_bc, field_stats)
@@ -170,9 +178,11 @@ class MarchStep(TrainStep):
         if field_stats is not None:
             field_stats.check_free()
         TB.check_owner(time_bc, graphs)
+        WF.check_owner("MarchStep", wall_forces, graphs)
         check_time_scheme(time_scheme)
         self._march = None
         self.field_stats = None
+        self.wall_forces = None
         self.time_bc = None
         super().__init__(model, graphs, use_graph=use_graph, **trainstep_kwargs)
         self._max_inner, self._min_inner, self._tol, self._abs_tol, self.max_levels, self.keep = args
@@ -194,6 +204,8 @@ class MarchStep(TrainStep):
         if field_stats is not None:
             # (attached last: the constructor above issues no step, so no list has been recorded without its launch)
             self.field_stats = field_stats.attach(self, self.x_backup)
+        if wall_forces is not None:
+            self.wall_forces = wall_forces.attach(self, graphs, pl, self.x_backup)
         if time_bc is not None:
             # (its attach issues the launch for level 0's field: the level count is 0)
             self.time_bc = time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._march, LEVEL, self.max_levels)
@@ -278,6 +290,9 @@ class MarchStep(TrainStep):
             # the clock is the level count: it moves on the launch that ends a level and on no other, so a level is sampled once,
             # whatever its inner count, and a held step samples nothing
             self.field_stats.launch(self.x_backup, self._march.data_ptr() + 4 * LEVEL)
+        if self.wall_forces is not None:
+            # the same clock: one row of the ring per completed level; it reads x_backup and the plan, writes only its own state
+            self.wall_forces.launch(self.x_backup, self._march.data_ptr() + 4 * LEVEL)
         if self.time_bc is not None:
             # the targets of level count + 1: new values behind the launch that ended a level, the same values again behind an inner
             # iteration or a held step (an early-out would need the blocks to agree on a "last" word: DESIGN.md 5u)
@@ -386,6 +401,8 @@ class MarchStep(TrainStep):
         self._put(TARGET, [self.max_levels])
         if self.field_stats is not None:
             self.field_stats.reset()
+        if self.wall_forces is not None:
+            self.wall_forces.reset()
         if self.time_bc is not None:
             self.time_bc.reset()                      # (behind the record's zero: the data of level 0's field)
         if self.time_scheme is not None:

@@ -48,6 +48,14 @@ records on the device (a ramped start-up, a pulsatile inlet, an oscillating lid,
 counter.  Eager steps and recorded lists carry it alike; `r.time_bc.read()` is what was applied, `set()` changes a waveform under
 a recorded list.  Refused together with `anderson` > 0 and for graphs of a DevicePool.  `time_bc=None` (the default) issues no
 new launch and allocates nothing.
+
+Wall forces (`wall_forces=WallForces(faces=, box=, origin=, start=, stride=, stop=, keep=)`; gfv/wallforce.py).  Two more
+launches behind the advance, beside the field-statistics launch and before the boundary-data launch, sum the pressure and the viscous
+force of the field just written over the selected wall faces, and their moments, per graph, into a device ring of the last `keep`
+samples - the drag and lift history of a cylinder or airfoil run - following the step counter.  Eager steps and recorded lists carry
+them alike; `r.wall_forces.read()` is the one synchronisation, `set_window()` moves the window under a recorded list.  Refused together
+with `anderson` > 0 (a steady user calls `gfv.wallforce.evaluate()` on the converged field) and for graphs of a DevicePool; allowed
+beside `field_stats` and `time_bc`.  `wall_forces=None` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -57,6 +65,7 @@ from . import anderson as AA
 from . import cmdlist
 from . import lib as L
 from . import timebc as TB
+from . import wallforce as WF
 from .fieldstats import FieldStats
 from .functions import require_gpu
 from .listcache import WARM, ListCache
@@ -90,12 +99,14 @@ class Rollout:
     WARM = WARM   # eager steps before a list is recorded (they are steps of the rollout like any other)
 
     def __init__(self, model, graphs, max_steps=1000, launch_mode="cmd_list", norm_global=None, anderson=0, anderson_beta=1.0,
-                 anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0, field_stats=None, time_bc=None):
+                 anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0, field_stats=None, time_bc=None,
+                 wall_forces=None):
         if launch_mode not in ("cmd_list", "eager"):
             raise ValueError('launch_mode must be "cmd_list" or "eager"')
         aa_args = AA.check_args(anderson, anderson_beta, anderson_reg, anderson_restart, anderson_start)
         check_field_stats(field_stats, aa_args[0])
         TB.check_owner(time_bc, graphs, aa_args[0])
+        WF.check_owner("Rollout", wall_forces, graphs, aa_args[0])
         graph_node = graphs[0]
         x = graph_node.x
         require_gpu(x)
@@ -131,6 +142,7 @@ class Rollout:
         self._fwd = StaticForward(model, pl.B, dev)
         # (attached last: should a line above raise, the FieldStats stays free for another owner)
         self.field_stats = None if field_stats is None else field_stats.attach(self, self.x_backup)
+        self.wall_forces = None if wall_forces is None else wall_forces.attach(self, graphs, pl, self.x_backup)
         # (its attach issues the launch for step 1: the step counter is 0)
         self.time_bc = None if time_bc is None else time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._state, 0,
                                                                    self.max_steps)
@@ -156,6 +168,8 @@ class Rollout:
             self.history.data_ptr(), self.max_steps, self._state.data_ptr(), L.stream_ptr()), "gfv_rollout_advance")
         if self.field_stats is not None:
             self.field_stats.launch(self.x_backup, self._state.data_ptr())     # (the clock: the step counter just advanced)
+        if self.wall_forces is not None:
+            self.wall_forces.launch(self.x_backup, self._state.data_ptr())     # (the same clock; it reads x_backup, writes its own)
         if self.time_bc is not None:
             self.time_bc.launch()                                              # (the targets of step counter + 1)
         L.status_publish()
@@ -203,7 +217,7 @@ class Rollout:
 
     def reset(self, x=None):
         """Back to step 0 from the initial node state (or from `x` [N,12], un-normalised); the history is cleared, the field
-        statistics (if any) start over and the boundary data (if any) are those of step 1 again."""
+        statistics and the wall forces (if any) start over and the boundary data (if any) are those of step 1 again."""
         src = self._x0 if x is None else x
         if x is not None:
             require_gpu(x)
@@ -217,6 +231,8 @@ class Rollout:
             self._aa.reset()
         if self.field_stats is not None:
             self.field_stats.reset()
+        if self.wall_forces is not None:
+            self.wall_forces.reset()
         if self.time_bc is not None:
             self.time_bc.reset()                                               # (behind the counter's zero: the data of step 1)
         self.steps_done = 0

@@ -1225,6 +1225,67 @@ int gfv_step_control_rows(const float* x_backup, const int32_t* batch, const flo
                           const int32_t* clock, const int32_t* rec, const float* state, float* ring, float* ustar, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Wall forces (gfv/wallforce.py): the pressure force and the viscous force of the fluid on a body and their moments,
+ * per graph, for the field a run has just written - the momentum flux the residual itself attributes to the wall faces (P_flux -
+ * vis_flux of FVscheme.py:203-229; the convective flux is left out: it is zero on a wall whose velocity has no normal component).
+ * TWO launches behind the launch that has advanced the field (gfv_rollout_advance, gfv_march_advance), on the same stream:
+ * gfv_wall_force_grad, then gfv_wall_force_sum.  `x_backup`, `clock` and the words of `rec` are gfv_field_stats_update's.
+ *   uvp_dim float [B, 3];  batch int32 [N];  theta float [B, ld_theta], ld_theta >= 5: columns 3 and 4 are read at every launch
+ *   x_rowptr int32 [N + 1], x_out int32 [S], x_B float [S, terms], An float [N, terms * terms], rn float [N, terms]: the WLSQ
+ *              stencil of the plan, as gfv_wlsq_fwd_ex takes it;  terms 2 / 5 / 9 / 14
+ *   pos float [N, 2], fpos float [E, 2], es, er int32 [E], kS float [Sg, 2]: node and face positions, a face's end nodes, the
+ *              surface vector of a (cell, face) incidence - the cell's OUTWARD vector, so on a wall face it points into the body
+ *   bnode      int32 [Nb]: the selected faces' end nodes, unique and ascending
+ *   wface      int32 [Nf, 4], 16-byte aligned: per selected face (f, k, ja, jb) - the face, its one incidence, the positions of
+ *              es[f] and er[f] in bnode; rows ascending in f, hence grouped by graph
+ *   wchunk_beg, wchunk_end int32 [n_wchunks], gwchunk_ptr int32 [B + 1]: chunks of at most GFV_WALL_FORCE_CHUNK consecutive rows
+ *              of wface that never cross a graph, and each graph's range of chunks (the form of a plan's chunk tables)
+ *   origin     float [B, 2] (host): the point the moments are taken about
+ *   gb         double [Nb, 3, 2]: the body nodes' gradients (written by the first launch, read by the second)
+ *   partial    double [n_wchunks, GFV_WALL_FORCE_SUMS]: workspace
+ *   hist       double [keep, B, GFV_WALL_FORCE_SUMS]: (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv) per graph, row n % keep
+ *   hist_clock int32 [keep]: the clock of a row
+ * The rule, with rec and *clock AS EACH LAUNCH FINDS THEM (every thread reads them before anything is written; only the last
+ * arriver of the second launch writes rec, so the pair decides alike):
+ *   c = *clock;  take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % max(stride, 1) == 0
+ *   take false:  the first launch reads and writes nothing; the second moves no word of partial, hist or hist_clock
+ *   take true:
+ *     phi_c(i) = x_backup[i, c] / uvp_dim[3 batch[i] + c], c = u, v, p: ONE fp32 division (gfv_step_control_rate's convention)
+ *     gb[j, c, 0:2], i = bnode[j]: the arithmetic of gfv_wlsq_fwd_ex - rhs_m = sum_s (double)x_B[s, m] * ((double)phi_c(x_out[s]) -
+ *       (double)phi_c(i)) over s = x_rowptr[i] .. x_rowptr[i + 1] - 1 ascending, from +0; rhs_m / (double)rn[i, m]; the matrix
+ *       (double)An[i, r, q] * (1 / (double)rn[i, r]); LU with partial pivoting and the solve in double - the first two entries of
+ *       the solution, kept in double
+ *     per row (f, k, ja, jb) of wface, graph b, s = es[f], r = er[f], S = kS[k], g_s = gb[ja], g_r = gb[jb]; everything below one
+ *     IEEE double operation in the order written, nothing contracted, except where fp32 is named:
+ *       r_s = fpos[f] - pos[s], r_r = fpos[f] - pos[r]                                  (fp32, as gfv_face_fwd forms them)
+ *       v_s = phi_p(s) + (r_s.x * g_s[p][0] + r_s.y * g_s[p][1]);  v_r likewise;  p_f = 0.5 * (v_s + v_r)
+ *       Fp = ((theta3 * p_f) * S.x, (theta3 * p_f) * S.y)
+ *       G[c][a] = 0.5 * (g_s[c][a] + g_r[c][a]), c = u, v;   Fv[c] = -(theta4 * (G[c][0] * S.x + G[c][1] * S.y))
+ *       arm = (double)fpos[f] - (double)origin[b];  Mp = arm.x * Fp.y - arm.y * Fp.x;  Mv likewise
+ *     (no wall overwrite of the face velocity: it concerns u, v, which nothing here reads.)  Fp + Fv is the force of the fluid
+ *     ON THE WALL.
+ *     per chunk: one wave; lane l adds the rows beg + l, beg + l + 64, ... < min(end, Nf) in ascending order from +0.0, the 64
+ *     lane sums fold by the xor butterfly 32, 16, ... 1; per graph, by the workgroup that arrives last: lane l adds the chunk
+ *     sums c0 + l, c0 + l + 64, ... in ascending order, then the same butterfly (csrc/gfv_reduce.h states the order)
+ *     hist[n % keep, b, :] = the graph's six sums (zero for a graph without a face);  hist_clock[n % keep] = c
+ *   then, always:  last = c if it differs;  n += 1 if take;  the counter back to 0
+ * No floating-point atomics and no sum across graphs: the same inputs give the same bits, whatever the grid.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, Nb, Nf, n_wchunks, B or keep < 1, ld_theta < 5, terms outside the four
+ * values, an x_backup or wface that is not 16-byte aligned, or a gb, partial or hist that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_WALL_FORCE_RECORD 8
+#define GFV_WALL_FORCE_SUMS 6
+#define GFV_WALL_FORCE_CHUNK 64
+int gfv_wall_force_grad(const float* x_backup, const float* uvp_dim, const int32_t* batch, const int32_t* x_rowptr,
+                        const int32_t* x_out, const float* x_B, const float* An, const float* rn, const int32_t* bnode, int32_t Nb,
+                        int32_t terms, const int32_t* clock, const int32_t* rec, double* gb, void* stream);
+int gfv_wall_force_sum(const float* x_backup, const float* uvp_dim, const float* theta, int32_t ld_theta, const float* pos,
+                       const float* fpos, const float* kS, const int32_t* es, const int32_t* er, const int32_t* wface,
+                       const int32_t* wchunk_beg, const int32_t* wchunk_end, const int32_t* gwchunk_ptr, int32_t n_wchunks,
+                       int32_t Nf, int32_t B, const float* origin, const double* gb, const int32_t* clock, int32_t* rec,
+                       double* partial, double* hist, int32_t* hist_clock, int32_t keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
  * at pre_train_Adam.py:203 and solve_with_grad_GPU.py:197, and torch.optim.lr_scheduler.ReduceLROnPlateau).  ONE launch of one
  * wave recomputes the rate from a device record and writes it where the Adam launches read it:
