@@ -2,15 +2,16 @@
 // of the node field over a window of a run, kept on the device.  ONE launch behind the launch that advances the field
 // (gfv_rollout_advance, gfv_march_advance); it follows a clock word that launch writes, the idea of GFV_SCHED_FOLLOW.
 //
-// With the record rec[8] (include/gfv.h) AS THE LAUNCH FINDS IT - every workgroup reads it and *clock before anything is written;
-// the workgroup that arrives last writes it (no-data arrival of gfv_reduce.h: it needs nothing another workgroup wrote):
-//   c = *clock;  take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % max(stride, 1) == 0
+// With the record rec[8] AS THE LAUNCH FINDS IT (the window: include/gfv.h GFV_WINDOW_RECORD, gfv_window.h) - every workgroup reads
+// it and *clock before anything is written; the workgroup that arrives last writes it (no-data arrival of gfv_reduce.h: it needs
+// nothing another workgroup wrote):
+//   c = *clock;  take = gfv_window_take(rec, c)
 //   take false:  no row and no state element is read or written
 //   take true:   per row, x = x_backup[i, 0:3]
 //     n == 0:    K = min = max = x; the seven sums = +0.0 (a reset needs no memset)
 //     n > 0:     d = (double)x - (double)K; S1 += d; S2uu += du * du; S2vv += dv * dv; S2pp += dp * dp; S2uv += du * dv (each
 //                product and each sum one double operation); min = fminf(min, x); max = fmaxf(max, x)
-//   last arriver: last = c if it differs; n += 1 if take; the counter back to 0
+//   last arriver: gfv_window_commit
 // One thread per row, no cross-row sum, no floating-point atomics: the same inputs give the same bits whatever the grid.  The state
 // is planar (sums [7, N], aux [9, N]): consecutive lanes touch consecutive addresses of every plane.
 #include "../../include/gfv.h"
@@ -18,21 +19,19 @@
 #include "gfv_launch.h"
 #include "gfv_prof.h"
 #include "gfv_reduce.h"
+#include "gfv_window.h"
 
 namespace {
 
 constexpr int FS_TPB = 256;
-enum { FS_START = 0, FS_STRIDE = 1, FS_STOP = 2, FS_LAST = 3, FS_N = 4, FS_COUNTER = 5, FS_ENABLED = 6 };
-static_assert(GFV_FIELD_STATS_RECORD == 8 && GFV_FIELD_STATS_SUMS == 7 && GFV_FIELD_STATS_AUX == 9, "include/gfv.h");
+static_assert(GFV_FIELD_STATS_SUMS == 7 && GFV_FIELD_STATS_AUX == 9, "include/gfv.h");
 
 __global__ __launch_bounds__(FS_TPB) void field_stats_kernel(const float* __restrict__ x_backup, int N, const int* clock, int* rec,
                                                              double* __restrict__ sums, float* __restrict__ aux) {
   // ---- the record and the clock as the launch finds them: read by every thread before the arrival below -----------------------
-  const int start = rec[FS_START], stride = max(rec[FS_STRIDE], 1), stop = rec[FS_STOP];
-  const int last = rec[FS_LAST], n = rec[FS_N], enabled = rec[FS_ENABLED];
   const int c = *clock;
-  const bool take = enabled != 0 && c != last && c >= start && (stop < 0 || c < stop) &&
-                    ((long long)c - (long long)start) % (long long)stride == 0;
+  const int last = rec[GFV_WIN_LAST], n = rec[GFV_WIN_N];
+  const bool take = gfv_window_take(rec, c);
   const int i = blockIdx.x * FS_TPB + threadIdx.x;
   if (take && i < N) {
     const size_t n_ = (size_t)N;
@@ -64,10 +63,8 @@ __global__ __launch_bounds__(FS_TPB) void field_stats_kernel(const float* __rest
       s[6 * n_] = s[6 * n_] + uv;
     }
   }
-  if (!gfv_arrive_last_nodata(rec + FS_COUNTER)) return;              // (true on thread 0 of the last workgroup only)
-  if (c != last) rec[FS_LAST] = c;
-  if (take) rec[FS_N] = n + 1;
-  rec[FS_COUNTER] = 0;
+  if (!gfv_arrive_last_nodata(rec + GFV_WIN_COUNTER)) return;         // (true on thread 0 of the last workgroup only)
+  gfv_window_commit(rec, c, last, n, take);
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // Wall forces (gfv/wallforce.py): the pressure and the viscous force of the fluid on a body, and their moment, per
 // graph and per sampled field, summed on the device.  TWO launches behind the launch that advances the field (gfv_rollout_advance,
-// gfv_march_advance); both follow the clock word that launch writes and read it, and the record rec[8] (the words of
-// gfv_field_stats_update), as they find them:
-//   c = *clock;  take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % max(stride, 1) == 0
+// gfv_march_advance); both follow the clock word that launch writes and read it, and the record rec[8] (the window: include/gfv.h
+// GFV_WINDOW_RECORD, gfv_window.h), as they find them:
+//   c = *clock;  take = gfv_window_take(rec, c)
 // Only the last arriver of the second launch writes the record, so the pair decides alike.
 //
 //   gfv_wall_force_grad   lane (j, c), c < 3, over the Nb end nodes of the selected faces: the WLSQ gradient of channel c at node
@@ -13,7 +13,7 @@
 //                         beg + l + 64, ... in ascending order, the 64 lane sums fold by gfv_wave_sum, one double per chunk and sum
 //                         goes to partial [n_wchunks, 6].  The workgroup that arrives last (all-fence form: the partials are plain
 //                         stores of other workgroups) folds them per graph (gfv_fold_chunks<6>, gfv_wave_sum) into the ring's row
-//                         n % keep, then: last = c if it differs; n += 1 if take; the counter back to 0.
+//                         n % keep, then gfv_window_commit.
 // take false: the first launch reads and writes nothing, the second moves no history word.  No floating-point atomics, no sum
 // across graphs, an order that does not depend on the grid: the same inputs give the same bits.  The rule in full: include/gfv.h.
 #include "../../include/gfv.h"
@@ -22,20 +22,12 @@
 #include "gfv_lu.h"
 #include "gfv_prof.h"
 #include "gfv_reduce.h"
+#include "gfv_window.h"
 
 namespace {
 
 constexpr int WF_TPB = 256;
-enum { WF_START = 0, WF_STRIDE = 1, WF_STOP = 2, WF_LAST = 3, WF_N = 4, WF_COUNTER = 5, WF_ENABLED = 6 };
-static_assert(GFV_WALL_FORCE_RECORD == 8 && GFV_WALL_FORCE_SUMS == 6 && GFV_WALL_FORCE_CHUNK == 64, "include/gfv.h");
-static_assert(GFV_WALL_FORCE_RECORD == GFV_FIELD_STATS_RECORD, "the record is gfv_field_stats_update's");
-
-static __device__ __forceinline__ bool wf_take(const int* rec, int c) {
-  const int start = rec[WF_START], stride = max(rec[WF_STRIDE], 1), stop = rec[WF_STOP];
-  const int last = rec[WF_LAST], enabled = rec[WF_ENABLED];
-  return enabled != 0 && c != last && c >= start && (stop < 0 || c < stop) &&
-         ((long long)c - (long long)start) % (long long)stride == 0;
-}
+static_assert(GFV_WALL_FORCE_SUMS == 6 && GFV_WALL_FORCE_CHUNK == 64, "include/gfv.h");
 
 // ---- 1. the body nodes' gradients: wlsq_fwd_kernel's arithmetic, 4 lanes per node (the fourth idle), the result in double ------
 template <int M>
@@ -45,7 +37,7 @@ __global__ __launch_bounds__(WF_TPB) void wall_grad_kernel(const float* __restri
                                                            const float* __restrict__ An, const float* __restrict__ rn,
                                                            const int* __restrict__ bnode, int Nb, const int* clock, const int* rec,
                                                            double* __restrict__ gb) {
-  if (!wf_take(rec, *clock)) return;
+  if (!gfv_window_take(rec, *clock)) return;
   const int t = blockIdx.x * WF_TPB + threadIdx.x;
   const int j = t >> 2, c = t & 3;
   if (j >= Nb || c >= 3) return;
@@ -114,8 +106,8 @@ struct SumArgs {
 __global__ __launch_bounds__(WF_TPB) void wall_sum_kernel(const SumArgs A) {
   // ---- the record and the clock as the launch finds them: read by every thread before the arrival below ----------------------
   const int c = *A.clock;
-  const int last = A.rec[WF_LAST], n = A.rec[WF_N];
-  const bool take = wf_take(A.rec, c);
+  const int last = A.rec[GFV_WIN_LAST], n = A.rec[GFV_WIN_N];
+  const bool take = gfv_window_take(A.rec, c);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int q = blockIdx.x * (WF_TPB / 64) + wave;
   if (take && q < A.n_wchunks) {
@@ -158,7 +150,7 @@ __global__ __launch_bounds__(WF_TPB) void wall_sum_kernel(const SumArgs A) {
       A.partial[(size_t)q * GFV_WALL_FORCE_SUMS + lane] = v;
     }
   }
-  if (!gfv_arrive_last_all_fence(A.rec + WF_COUNTER)) return;
+  if (!gfv_arrive_last_all_fence(A.rec + GFV_WIN_COUNTER)) return;
   // ---- the fold, per graph: every partial is in place -------------------------------------------------------------------------
   if (take) {
     const size_t slot = (size_t)((unsigned)n % (unsigned)A.keep);
@@ -175,11 +167,7 @@ __global__ __launch_bounds__(WF_TPB) void wall_sum_kernel(const SumArgs A) {
     }
     if (threadIdx.x == 0) A.hist_clock[slot] = c;
   }
-  if (threadIdx.x == 0) {
-    if (c != last) A.rec[WF_LAST] = c;
-    if (take) A.rec[WF_N] = n + 1;
-    A.rec[WF_COUNTER] = 0;                      // (reusable by the next launch)
-  }
+  if (threadIdx.x == 0) gfv_window_commit(A.rec, c, last, n, take);
 }
 
 }  // namespace

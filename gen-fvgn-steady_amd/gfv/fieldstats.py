@@ -13,10 +13,8 @@ host never synchronises per step; `FieldStats` is one small launch behind the la
     fs.set_window(stride=1)                                # recorded lists follow it: nothing is recorded again
     ms = MarchStep(model, graphs, ..., field_stats=FieldStats(start=1))   # one sample per completed level (the first is 1)
 
-The clock counts fields written: the field the first step (the first completed level) leaves has clock 1; clock 0 is the initial
-state, which is never sampled (`start` is at least 1).  A clock value is
-sampled when `start <= clock < stop` and `(clock - start) % stride == 0`, once (a `MarchStep` step that does not end a level, or
-is held, leaves the clock as it is and samples nothing).
+Which fields are sampled: gfv/window.py (a `MarchStep` step that does not end a level, or is held, leaves the clock as it is and
+samples nothing).  How the object is handed over, attached and launched: gfv/follow.py.
 
 What is kept, per node and channel: the shift K (the first sample), S1 = sum (x - K), S2 = sum (x - K)^2 and sum (u - Ku)(v - Kv)
 in float64, the minimum and the maximum.  Shifted by the first sample the sums are of the size of the fluctuation, so a mean a
@@ -29,36 +27,12 @@ never reallocated: the record, the sums and the shift / extremes.  One owner per
 """
 from __future__ import annotations
 
-import numbers
-
 import torch
 
 from . import lib as L
-
-# words of the record (include/gfv.h gfv_field_stats_update)
-START, STRIDE, STOP, LAST, N_SAMPLES, COUNTER, ENABLED = range(7)
-NO_STOP = -1    # a negative stop is no stop
-UNCHANGED = object()    # set_window(stop=): None already means "no end"
-
-
-def check_field_stats_args(start=1, stride=1, stop=None, enabled=True):
-    """The window's checks; needs no GPU.  -> (start, stride, stop, enabled) as the record's words, stop None as NO_STOP."""
-    for name, v in (("start", start), ("stride", stride)) + ((("stop", stop),) if stop is not None else ()):
-        if isinstance(v, bool) or not isinstance(v, numbers.Integral):
-            raise ValueError(f"{name} must be an integer, got {v!r}")
-        if v >= 2 ** 31:
-            raise ValueError(f"{name} must be below 2^31, got {v!r}")
-    if start < 1:
-        # clock 0 is the INITIAL state: a MarchStep's level word is 0 until its first level ends, so start = 0 would sample the
-        # field nobody has advanced yet (a Rollout's launch never sees clock 0)
-        raise ValueError(f"start must be at least 1 (the first field written has clock 1; clock 0 is the initial state), got {start}")
-    if stride < 1:
-        raise ValueError(f"stride must be at least 1, got {stride}")
-    if stop is not None and stop < 0:
-        raise ValueError(f"stop must be None (no end) or at least 0 (exclusive), got {stop}")
-    if not isinstance(enabled, (bool, numbers.Integral)):
-        raise ValueError(f"enabled must be a bool, got {enabled!r}")
-    return int(start), int(stride), NO_STOP if stop is None else int(stop), 1 if enabled else 0
+from .follow import Follower
+from .window import (COUNTER, ENABLED, LAST, N_SAMPLES, NO_STOP, START, STOP, STRIDE, UNCHANGED, Window,  # noqa: F401  (re-exports)
+                     check_window_args as check_field_stats_args)
 
 
 def check_field(x_backup):
@@ -86,77 +60,53 @@ def moments(n, sums, aux):
             "min": aux[3:6].t().contiguous(), "max": aux[6:9].t().contiguous()}
 
 
-class FieldStats:
+class FieldStats(Follower):
+    KEYWORD = "field_stats"
+    NO_ANDERSON = "their mean and variance are not the flow's"
+
     def __init__(self, start=1, stride=1, stop=None):
-        self._window = check_field_stats_args(start, stride, stop, True)
+        self._window = Window(start, stride, stop)
         self.rec = self.sums = self.aux = None        # device state: allocated by attach(), never reallocated
-        self._owner = None                            # the owner's class name once attached - NOT the owner: a reference back
-        self.N = 0                                    # would tie the two into a cycle and keep the owner's recorded lists (and
-                                                      # a MarchStep's pinned mirror) alive until a garbage collection
+        self.N = 0
 
-    start = property(lambda self: self._window[0])
-    stride = property(lambda self: self._window[1])
-    stop = property(lambda self: None if self._window[2] < 0 else self._window[2])
-    enabled = property(lambda self: bool(self._window[3]))
+    start = property(lambda self: self._window.start)
+    stride = property(lambda self: self._window.stride)
+    stop = property(lambda self: self._window.stop)
+    enabled = property(lambda self: self._window.enabled)
 
-    # ---- the owner's side -------------------------------------------------------------------------------------------------------
-    def check_free(self):
-        """Needs no GPU: an owner's constructor calls it before it looks at anything else."""
-        if self._owner is not None:
-            raise ValueError(f"this FieldStats is already attached to a {self._owner} (one owner per object: it follows one "
-                             "clock)")
-
-    def attach(self, owner, x_backup):
-        """Called by the owner's constructor with the tensor it advances: allocates the record and the state (once).  -> self"""
+    # ---- the owner's side (gfv/follow.py) -------------------------------------------------------------------------------------
+    def attach(self, owner, x_backup, clock, clock_word=0):
+        """Called by the owner's constructor with the tensor it advances, its int32 record `clock` and the word of it that counts
+        the fields written: allocates the record and the state (once).  -> self"""
         self.check_free()
         n = check_field(x_backup)
         dev = x_backup.device
-        rec = torch.zeros(L.FIELD_STATS_RECORD, dtype=torch.int32, device=dev)
         sums = torch.zeros((L.FIELD_STATS_SUMS, n), dtype=torch.float64, device=dev)
         aux = torch.zeros((L.FIELD_STATS_AUX, n), dtype=torch.float32, device=dev)
-        self.N, self.rec, self.sums, self.aux = n, rec, sums, aux
-        self._write_window()
-        self.reset()
-        self._owner = type(owner).__name__       # (last: an attach that raised leaves the object free)
+        self._xb, self._clock, self._clock_ptr = x_backup, clock, clock.data_ptr() + 4 * int(clock_word)
+        self.N, self.rec, self.sums, self.aux = n, self._window.attach(dev), sums, aux
+        self._claim(owner)
         return self
 
-    def launch(self, x_backup, clock_ptr):
+    def launch(self):
         """The one launch, behind the owner's advance: part of the step body (eager steps and recorded lists carry it alike)."""
-        L.check(L.load().gfv_field_stats_update(x_backup.data_ptr(), self.N, clock_ptr, self.rec.data_ptr(), self.sums.data_ptr(),
-                                                self.aux.data_ptr(), L.stream_ptr()), "gfv_field_stats_update")
-
-    def _need(self):
-        if self.rec is None:
-            raise RuntimeError("this FieldStats is not attached yet: hand it to Rollout(..., field_stats=) or "
-                               "MarchStep(..., field_stats=)")
-
-    # ---- the record's host-written words ---------------------------------------------------------------------------------------
-    def _write_window(self):
-        w = self._window
-        self.rec[START:STOP + 1].copy_(torch.tensor(w[0:3], dtype=torch.int32))
-        self.rec[ENABLED:ENABLED + 1].copy_(torch.tensor(w[3:4], dtype=torch.int32))
+        L.check(L.load().gfv_field_stats_update(self._xb.data_ptr(), self.N, self._clock_ptr, self.rec.data_ptr(),
+                                                self.sums.data_ptr(), self.aux.data_ptr(), L.stream_ptr()), "gfv_field_stats_update")
 
     def set_window(self, start=None, stride=None, stop=UNCHANGED, enabled=None):
-        """A new window (None: unchanged; `stop=None` removes the end, leaving `stop` out keeps it), checked before anything
-        changes.  It reaches recorded lists through the device record: nothing is recorded again.  It holds from the next step
-        issued.  The statistics so far stay: reset() starts over."""
-        w = self._window
-        self._window = check_field_stats_args(w[0] if start is None else start, w[1] if stride is None else stride,
-                                              self.stop if stop is UNCHANGED else stop, bool(w[3]) if enabled is None else enabled)
-        if self.rec is not None:
-            self._write_window()
+        """`Window.set`: a new window under recorded lists.  The statistics so far stay: reset() starts over."""
+        self._window.set(start, stride, stop, enabled)
 
     def reset(self):
-        """Start over: last = -1, n = 0, in stream order.  The sums need no clearing (the first sample writes every element).  The
-        owner's reset() calls it; called alone, the next launch finds a clock it has not seen and samples it if the window holds."""
+        """`Window.reset`; the owner's reset() calls it.  The sums need no clearing (the first sample writes every element)."""
         self._need()
-        self.rec[LAST:N_SAMPLES + 1].copy_(torch.tensor([-1, 0], dtype=torch.int32))
+        self._window.reset()
 
     # ---- reading (each of these is one synchronisation) ----------------------------------------------------------------------
     def count(self):
         """Samples taken so far."""
         self._need()
-        return int(self.rec[N_SAMPLES:N_SAMPLES + 1].cpu()[0])
+        return self._window.count()
 
     def read(self):
         """{"n", "mean" [N,3], "var" [N,3], "cov_uv" [N], "min" [N,3], "max" [N,3]} as CPU tensors; raises with n == 0.

@@ -110,8 +110,9 @@ EVAL_RECORD = 16   # GFV_EVAL_RECORD of include/gfv.h: floats per row of the tab
 TRAIN_LOG_CHUNK, TRAIN_LOG_HEAD, TRAIN_LOG_ENTRY_RECORD, TRAIN_LOG_MAX_BUCKETS = 1024, 16, 8, 32
 # GFV_MARCH_* of include/gfv.h: words of the march record, head words and per-graph words of a history row, the two flags
 MARCH_RECORD, MARCH_HEAD, MARCH_GRAPH, MARCH_CONVERGED, MARCH_CAPPED = 16, 8, 8, 1, 2
-# GFV_FIELD_STATS_* of include/gfv.h: words of the record, planes of the double sums, planes of the float state
-FIELD_STATS_RECORD, FIELD_STATS_SUMS, FIELD_STATS_AUX = 8, 7, 9
+WINDOW_RECORD = 8   # GFV_WINDOW_RECORD of include/gfv.h: words of a sampling window's record
+# GFV_FIELD_STATS_* of include/gfv.h: words of the record (the window's), planes of the double sums, planes of the float state
+FIELD_STATS_RECORD, FIELD_STATS_SUMS, FIELD_STATS_AUX = WINDOW_RECORD, 7, 9
 # GFV_TIME_BC_* of include/gfv.h: doubles of a waveform record, words of the control record, doubles of a history row, points of a
 # table at most, the kinds of gfv_time_bc_update
 TIME_BC_RECORD, TIME_BC_CTL, TIME_BC_HIST, TIME_BC_TABLE_MAX = 8, 4, 3, 1024
@@ -120,8 +121,8 @@ TIME_BC_NONE, TIME_BC_CONST, TIME_BC_RAMP_LINEAR, TIME_BC_RAMP_SMOOTH, TIME_BC_S
 TIME_SCHEME_RECORD, TIME_SCHEME_BDF1, TIME_SCHEME_BDF2 = 4, 1, 2
 # GFV_STEP_CONTROL_* of include/gfv.h: words of the control record, floats of the parameters, rows of the per-graph state
 STEP_CONTROL_RECORD, STEP_CONTROL_PARAMS, STEP_CONTROL_STATE = 4, 8, 4
-# GFV_WALL_FORCE_* of include/gfv.h: words of the record (gfv_field_stats_update's), sums per graph, faces per chunk at most
-WALL_FORCE_RECORD, WALL_FORCE_SUMS, WALL_FORCE_CHUNK = 8, 6, 64
+# GFV_WALL_FORCE_* of include/gfv.h: words of the record (the window's), sums per graph, faces per chunk at most
+WALL_FORCE_RECORD, WALL_FORCE_SUMS, WALL_FORCE_CHUNK = WINDOW_RECORD, 6, 64
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2

@@ -87,11 +87,9 @@ import struct
 import torch
 
 from . import lib as L
-from . import timebc as TB
-from . import wallforce as WF
-from .fieldstats import FieldStats
+from .follow import check_followers
 from .schedule import Plateau
-from .timescheme import check_adapt_owner, check_owner as check_time_scheme
+from .timescheme import check_adapt_owner
 from .trainer import TrainStep
 
 # words of the march record (include/gfv.h gfv_march_advance)
@@ -173,17 +171,11 @@ class MarchStep(TrainStep):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
         check_adapt_owner("MarchStep", time_scheme, time_bc, field_stats)
-        if field_stats is not None and not isinstance(field_stats, FieldStats):
-            raise ValueError(f"MarchStep: field_stats must be a gfv.fieldstats.FieldStats or None, got {field_stats!r}")
-        if field_stats is not None:
-            field_stats.check_free()
-        TB.check_owner(time_bc, graphs)
-        WF.check_owner("MarchStep", wall_forces, graphs)
-        check_time_scheme(time_scheme)
+        check_followers("MarchStep", graphs, 0, field_stats=field_stats, wall_forces=wall_forces, time_bc=time_bc,
+                        time_scheme=time_scheme)
         self._march = None
-        self.field_stats = None
-        self.wall_forces = None
-        self.time_bc = None
+        self.field_stats = self.wall_forces = self.time_bc = None
+        self._followers = []
         super().__init__(model, graphs, use_graph=use_graph, **trainstep_kwargs)
         self._max_inner, self._min_inner, self._tol, self._abs_tol, self.max_levels, self.keep = args
         dev, pl = self.dev, self.plan
@@ -201,17 +193,18 @@ class MarchStep(TrainStep):
         self._mirror, self._mirror_dev = host, devp.value
         self._write_control()
         self._put(TARGET, [self.max_levels])     # (step() on its own marches until the history is full)
-        if field_stats is not None:
-            # (attached last: the constructor above issues no step, so no list has been recorded without its launch)
-            self.field_stats = field_stats.attach(self, self.x_backup)
-        if wall_forces is not None:
-            self.wall_forces = wall_forces.attach(self, graphs, pl, self.x_backup)
-        if time_bc is not None:
-            # (its attach issues the launch for level 0's field: the level count is 0)
-            self.time_bc = time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._march, LEVEL, self.max_levels)
-        if time_scheme is not None:
-            # (its attach issues the launch for level 0: the baseline of the initial field, second order with `previous=`)
-            self.time_scheme = time_scheme.attach(self, pl, self.x_backup, self._march, LEVEL)
+        # The followers of the level count (gfv/follow.py), attached last: the constructor above issues no step, so no list has been
+        # recorded without their launches.  The clock is word LEVEL of the march record: it moves on the launch that ends a level and
+        # on no other, so each acts once per level, whatever its inner count: behind an inner iteration or a held step the samplers
+        # sample nothing, and time_bc (the targets of level count + 1) and time_scheme (the ring's rotation, the next level's baseline)
+        # write the same bits again (an early-out would need the blocks to agree on a "last" word: DESIGN.md 5u); the attach of each
+        # of those two issues its launch for level 0 (the level count is 0; second order with `previous=`).  They touch disjoint data
+        # (wall_forces reads x_backup and the plan) and none reads what another writes: their order among themselves does not matter.
+        self.field_stats = field_stats and field_stats.attach(self, self.x_backup, self._march, LEVEL)
+        self.wall_forces = wall_forces and wall_forces.attach(self, graphs, pl, self.x_backup, self._march, LEVEL)
+        self.time_bc = time_bc and time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._march, LEVEL, self.max_levels)
+        self.time_scheme = time_scheme and time_scheme.attach(self, pl, self.x_backup, self._march, LEVEL)
+        self._followers = [f for f in (self.field_stats, self.wall_forces, self.time_bc, self.time_scheme) if f is not None]
 
     def __del__(self):
         host = getattr(self, "_mirror", None)
@@ -283,24 +276,9 @@ class MarchStep(TrainStep):
         self._follow_level()
 
     def _follow_level(self):
-        """The launches that follow the level count, behind the march launch.  They touch disjoint data (the statistics; the
-        boundary targets and the source column; the velocity ring and the time difference's two tensors) and none reads what
-        another writes: their order among themselves does not matter."""
-        if self.field_stats is not None:
-            # the clock is the level count: it moves on the launch that ends a level and on no other, so a level is sampled once,
-            # whatever its inner count, and a held step samples nothing
-            self.field_stats.launch(self.x_backup, self._march.data_ptr() + 4 * LEVEL)
-        if self.wall_forces is not None:
-            # the same clock: one row of the ring per completed level; it reads x_backup and the plan, writes only its own state
-            self.wall_forces.launch(self.x_backup, self._march.data_ptr() + 4 * LEVEL)
-        if self.time_bc is not None:
-            # the targets of level count + 1: new values behind the launch that ended a level, the same values again behind an inner
-            # iteration or a held step (an early-out would need the blocks to agree on a "last" word: DESIGN.md 5u)
-            self.time_bc.launch()
-        if self.time_scheme is not None:
-            # the ring's rotation and the next level's baseline behind the launch that ended a level; the same bits again behind an
-            # inner iteration or a held step.  It touches nothing the two launches above touch: their order does not matter
-            self.time_scheme.launch()
+        """The launches that follow the level count, behind the march launch (which, and why there: the constructor)."""
+        for f in self._followers:
+            f.launch()
 
     def _hold_record(self):
         return self._march       # (word [3] = APPLY: the march launch of this step wrote it; the guard, Adam and the log read it)
@@ -399,14 +377,8 @@ class MarchStep(TrainStep):
             self._mirror[i] = 0
         self._write_control()
         self._put(TARGET, [self.max_levels])
-        if self.field_stats is not None:
-            self.field_stats.reset()
-        if self.wall_forces is not None:
-            self.wall_forces.reset()
-        if self.time_bc is not None:
-            self.time_bc.reset()                      # (behind the record's zero: the data of level 0's field)
-        if self.time_scheme is not None:
-            self.time_scheme.reset()                  # (behind the record's zero: base = 0, level 0 is first order again)
+        for f in self._followers:
+            f.reset()                                 # (behind the record's zero: the data of level 0's field; base = 0)
 
     # ---- checkpoints -----------------------------------------------------------------------------------------------------------
     def state_dict(self):

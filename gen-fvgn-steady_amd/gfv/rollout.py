@@ -64,9 +64,8 @@ import torch
 from . import anderson as AA
 from . import cmdlist
 from . import lib as L
-from . import timebc as TB
-from . import wallforce as WF
 from .fieldstats import FieldStats
+from .follow import check_followers
 from .functions import require_gpu
 from .listcache import WARM, ListCache
 from .plan import get_plan
@@ -85,14 +84,7 @@ def check_room(steps_done, max_steps, steps=1):
 
 def check_field_stats(field_stats, anderson):
     """What a Rollout refuses of `field_stats=`; needs no GPU."""
-    if field_stats is None:
-        return
-    if not isinstance(field_stats, FieldStats):
-        raise ValueError(f"field_stats must be a gfv.fieldstats.FieldStats or None, got {field_stats!r}")
-    field_stats.check_free()
-    if anderson:
-        raise ValueError("Rollout: anderson > 0 together with field_stats is not supported (accelerated iterates are not time "
-                         "steps of the model: their mean and variance are not the flow's)")
+    FieldStats.check_handed("Rollout", field_stats, None, anderson)
 
 
 class Rollout:
@@ -104,9 +96,7 @@ class Rollout:
         if launch_mode not in ("cmd_list", "eager"):
             raise ValueError('launch_mode must be "cmd_list" or "eager"')
         aa_args = AA.check_args(anderson, anderson_beta, anderson_reg, anderson_restart, anderson_start)
-        check_field_stats(field_stats, aa_args[0])
-        TB.check_owner(time_bc, graphs, aa_args[0])
-        WF.check_owner("Rollout", wall_forces, graphs, aa_args[0])
+        check_followers("Rollout", graphs, aa_args[0], field_stats=field_stats, wall_forces=wall_forces, time_bc=time_bc)
         graph_node = graphs[0]
         x = graph_node.x
         require_gpu(x)
@@ -140,12 +130,13 @@ class Rollout:
         self._lists = ListCache(None, dev=dev)      # accumulate -> the recorded step; unbounded: two keys at most
         self._outs = None
         self._fwd = StaticForward(model, pl.B, dev)
-        # (attached last: should a line above raise, the FieldStats stays free for another owner)
-        self.field_stats = None if field_stats is None else field_stats.attach(self, self.x_backup)
-        self.wall_forces = None if wall_forces is None else wall_forces.attach(self, graphs, pl, self.x_backup)
-        # (its attach issues the launch for step 1: the step counter is 0)
-        self.time_bc = None if time_bc is None else time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._state, 0,
-                                                                   self.max_steps)
+        # The followers of the step counter (gfv/follow.py; word 0 of _state), attached last: should a line above raise, they stay
+        # free for another owner.  Behind the advance field_stats samples the field just written, wall_forces reads it and the plan and
+        # writes only its own state, time_bc writes the targets of step counter + 1 (its attach: those of step 1, the counter is 0).
+        self.field_stats = field_stats and field_stats.attach(self, self.x_backup, self._state, 0)
+        self.wall_forces = wall_forces and wall_forces.attach(self, graphs, pl, self.x_backup, self._state, 0)
+        self.time_bc = time_bc and time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._state, 0, self.max_steps)
+        self._followers = [f for f in (self.field_stats, self.wall_forces, self.time_bc) if f is not None]
 
     # ---- weights -------------------------------------------------------------------------------------------------------
     def refresh_weights(self):
@@ -166,12 +157,8 @@ class Rollout:
             uvp_node.data_ptr(), self.x_backup.data_ptr(), self.x.data_ptr(), pl.N, pl.chunk_beg.data_ptr(),
             pl.chunk_end.data_ptr(), pl.gchunk_ptr.data_ptr(), pl.n_chunks, pl.B, losses.data_ptr(), self._partial.data_ptr(),
             self.history.data_ptr(), self.max_steps, self._state.data_ptr(), L.stream_ptr()), "gfv_rollout_advance")
-        if self.field_stats is not None:
-            self.field_stats.launch(self.x_backup, self._state.data_ptr())     # (the clock: the step counter just advanced)
-        if self.wall_forces is not None:
-            self.wall_forces.launch(self.x_backup, self._state.data_ptr())     # (the same clock; it reads x_backup, writes its own)
-        if self.time_bc is not None:
-            self.time_bc.launch()                                              # (the targets of step counter + 1)
+        for f in self._followers:
+            f.launch()
         L.status_publish()
         return losses, uvp_node, uvp_cell
 
@@ -229,12 +216,8 @@ class Rollout:
         self._state.zero_()
         if self._aa is not None:
             self._aa.reset()
-        if self.field_stats is not None:
-            self.field_stats.reset()
-        if self.wall_forces is not None:
-            self.wall_forces.reset()
-        if self.time_bc is not None:
-            self.time_bc.reset()                                               # (behind the counter's zero: the data of step 1)
+        for f in self._followers:
+            f.reset()                                                          # (behind the counter's zero)
         self.steps_done = 0
         self._outs = None
 

@@ -50,6 +50,7 @@ import weakref
 import torch
 
 from . import lib as L
+from .follow import Follower
 
 NODE_TYPES = {"inflow": 1, "wall": 3, "in_wall": 5}      # utils/utilities.py NodeType
 DEFAULT_NODES = ("inflow", "in_wall")
@@ -211,36 +212,27 @@ def check_graphs(graphs):
 
 def check_owner(time_bc, graphs=None, anderson=0):
     """What an owner refuses of `time_bc=`; needs no GPU."""
-    if time_bc is None:
-        return
-    if not isinstance(time_bc, TimeBC):
-        raise ValueError(f"time_bc must be a gfv.timebc.TimeBC or None, got {time_bc!r}")
-    time_bc.check_free()
-    if anderson:
-        raise ValueError("Rollout: anderson > 0 together with time_bc is not supported (accelerated iterates are not time steps of "
-                         "the model: a boundary condition that follows the step count has no meaning for them)")
-    if graphs is not None:
-        check_graphs(graphs)
-        time_bc.resolve(int(graphs[4].theta_PDE.shape[0]))
+    TimeBC.check_handed(None, time_bc, graphs, anderson)
 
 
-class TimeBC:
+class TimeBC(Follower):
+    KEYWORD = "time_bc"
+    NO_ANDERSON = "a boundary condition that follows the step count has no meaning for them"
+
     def __init__(self, velocity=None, source=None, nodes=DEFAULT_NODES):
         self._velocity, self._source, self.type_mask = check_time_bc_args(velocity, source, nodes)
         self.nodes = (nodes,) if isinstance(nodes, str) else tuple(nodes)
         self.channels = (1 if self._velocity is not None else 0) | (2 if self._source is not None else 0)
-        self._owner = None          # the owner's class name once attached (FieldStats' rule: no strong reference back)
         self._owner_ref = None
         self.rec = self.tab = self.ctl = self.hist = self.y0 = self.theta0 = None    # device state: allocated by attach(), never
         self._scratch = None                                                         # reallocated (evaluate()'s scratch: on first use)
         self._waves = None          # [B][2] waveforms (None for a channel that is off)
         self._offset = 0
 
-    # ---- the owner's side -------------------------------------------------------------------------------------------------------
-    def check_free(self):
-        """Needs no GPU: an owner's constructor calls it before it looks at anything else."""
-        if self._owner is not None:
-            raise ValueError(f"this TimeBC is already attached to a {self._owner} (one owner per object: it follows one clock)")
+    # ---- the owner's side (gfv/follow.py) -------------------------------------------------------------------------------------
+    def _check_graphs(self, graphs):
+        check_graphs(graphs)
+        self.resolve(int(graphs[4].theta_PDE.shape[0]))
 
     def resolve(self, B):
         """-> (velocity, source) as one waveform per graph (or None); refuses a list whose length is not B.  Needs no GPU."""
@@ -275,8 +267,8 @@ class TimeBC:
                 if ws is not None:
                     self._write_wave(b, ch, ws[b])
         self.launch()
-        self._owner_ref = weakref.ref(owner)
-        self._owner = type(owner).__name__          # (last: an attach that raised leaves the object free)
+        self._owner_ref = weakref.ref(owner)        # (weak: rebase() tells a TrainStep that the plan is fresh)
+        self._claim(owner)
         return self
 
     def launch(self):
@@ -311,10 +303,6 @@ class TimeBC:
     def _set_offset(self, offset):
         self._offset = offset
         self.ctl[0:1].copy_(torch.tensor([offset], dtype=torch.int32))
-
-    def _need(self):
-        if self.rec is None:
-            raise RuntimeError("this TimeBC is not attached yet: hand it to Rollout(..., time_bc=) or MarchStep(..., time_bc=)")
 
     # ---- the records ---------------------------------------------------------------------------------------------------------------
     def _write_wave(self, b, ch, w):

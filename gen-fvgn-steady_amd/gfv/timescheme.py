@@ -72,6 +72,7 @@ import numbers
 import torch
 
 from . import lib as L
+from .follow import Follower
 
 SCHEMES = {"bdf1": L.TIME_SCHEME_BDF1, "bdf2": L.TIME_SCHEME_BDF2}
 SCHEME, BASE = 0, 1        # words of the record (include/gfv.h gfv_time_scheme_update)
@@ -134,11 +135,7 @@ def check_time_scheme_args(scheme, previous, adapt=None):
 
 def check_owner(time_scheme):
     """What an owner refuses of `time_scheme=`; needs no GPU."""
-    if time_scheme is None:
-        return
-    if not isinstance(time_scheme, TimeScheme):
-        raise ValueError(f"time_scheme must be a gfv.timescheme.TimeScheme or None, got {time_scheme!r}")
-    time_scheme.check_free()
+    TimeScheme.check_handed(None, time_scheme)
 
 
 def check_adapt_owner(who, time_scheme, time_bc=None, field_stats=None):
@@ -164,7 +161,10 @@ def check_field(x_backup, N):
                          "path)")
 
 
-class TimeScheme:
+class TimeScheme(Follower):
+    KEYWORD = "time_scheme"
+    OWNERS = ("MarchStep", "TrainStep")
+
     def __init__(self, scheme="bdf2", previous=None, adapt=None):
         self._word, self._previous = check_time_scheme_args(scheme, previous, adapt)
         self.scheme = scheme
@@ -173,16 +173,9 @@ class TimeScheme:
         self.ring = self.ustar = self.dt_eff = self.rec = None    # device state: allocated by attach(), never reallocated
         self._own_clock = None
         self._tbase = 0
-        self._owner = None                                        # the owner's class name once attached (FieldStats' rule)
         self._base = 0
 
-    # ---- the owner's side -------------------------------------------------------------------------------------------------------
-    def check_free(self):
-        """Needs no GPU: an owner's constructor calls it before it looks at anything else."""
-        if self._owner is not None:
-            raise ValueError(f"this TimeScheme is already attached to a {self._owner} (one owner per object: it follows one clock "
-                             "and holds one batch's history)")
-
+    # ---- the owner's side (gfv/follow.py) -------------------------------------------------------------------------------------
     def attach(self, owner, plan, x_backup, clock=None, clock_word=0):
         """Called by the owner's constructor, last: `clock` is the owner's int32 record and `clock_word` the word of it that counts
         the fields written (None: a word of this object's own, bumped by `tick()`).  Allocates the device state (once), installs
@@ -210,7 +203,7 @@ class TimeScheme:
         else:
             self.install_previous(prev)
         self._previous = None                   # (the ring holds it now)
-        self._owner = type(owner).__name__      # (last: an attach that raised leaves the object free)
+        self._claim(owner)
         return self
 
     def _alloc_control(self, plan, dev):
@@ -263,11 +256,6 @@ class TimeScheme:
         self.launch()
 
     time_state = property(lambda self: (self.ustar, self.dt_eff))
-
-    def _need(self):
-        if self.rec is None:
-            raise RuntimeError("this TimeScheme is not attached yet: hand it to MarchStep(..., time_scheme=) or "
-                               "TrainStep(..., time_scheme=)")
 
     def _read_clock(self):
         """(synchronises) the clock as the device holds it."""

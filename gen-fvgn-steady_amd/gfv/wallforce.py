@@ -4,7 +4,7 @@ A cylinder or airfoil run is made for the force on the body: the drag and lift h
 shedding frequency from the lift signal.  `Rollout` and `MarchStep` exist so that the host never synchronises per step;
 `WallForces` is two small launches behind the launch that advances the field (`gfv_wall_force_grad`, `gfv_wall_force_sum`;
 csrc/wallforce.hip, include/gfv.h), following the owner's clock - `Rollout`'s step counter, `MarchStep`'s level count - the way
-`FieldStats` does, with `FieldStats`' window rule word for word:
+`FieldStats` does (gfv/follow.py), sampling the fields of the same window rule (gfv/window.py):
 
     wf = WallForces(box=(0.05, 0.35, 0.08, 0.32), origin=(0.2, 0.2), start=1, stride=1, stop=None, keep=4096)
     r = Rollout(model, graphs, max_steps=2000, wall_forces=wf)
@@ -48,8 +48,9 @@ import numbers
 import torch
 
 from . import lib as L
-from .fieldstats import (COUNTER, ENABLED, LAST, N_SAMPLES, START, STOP, STRIDE, UNCHANGED,  # noqa: F401  (the record's words)
-                         check_field, check_field_stats_args)
+from .fieldstats import check_field
+from .follow import Follower
+from .window import N_SAMPLES, UNCHANGED, Window
 
 WALL_BOUNDARY = 3
 TERMS = (2, 5, 9, 14)
@@ -129,17 +130,7 @@ def check_graphs(graphs):
 
 def check_owner(who, wall_forces, graphs=None, anderson=0):
     """What an owner refuses of `wall_forces=`; needs no GPU."""
-    if wall_forces is None:
-        return
-    if not isinstance(wall_forces, WallForces):
-        raise ValueError(f"{who}: wall_forces must be a gfv.wallforce.WallForces or None, got {wall_forces!r}")
-    wall_forces.check_free()
-    if anderson:
-        raise ValueError(f"{who}: anderson > 0 together with wall_forces is not supported (accelerated iterates are not time steps "
-                         "of the model: the ring would record forces of fields that are not steps; call "
-                         "gfv.wallforce.evaluate() on the converged field)")
-    if graphs is not None:
-        check_graphs(graphs)
+    WallForces.check_handed(who, wall_forces, graphs, anderson)
 
 
 # ---- selection and tables: plain torch ops on whatever device the graphs live on ----------------------------------------------
@@ -252,9 +243,12 @@ def split_history(n, keep, hist, hist_clock):
     return hist_clock[order].clone(), hist[order].clone()
 
 
-class WallForces:
+class WallForces(Follower):
+    KEYWORD = "wall_forces"
+    NO_ANDERSON = "the ring would record forces of fields that are not steps; call gfv.wallforce.evaluate() on the converged field"
+
     def __init__(self, faces=None, box=None, origin=(0.0, 0.0), start=1, stride=1, stop=None, keep=4096):
-        self._window = check_field_stats_args(start, stride, stop, True)
+        self._window = Window(start, stride, stop)
         self.keep = check_keep(keep)
         check_box(box)
         check_origin(origin)
@@ -267,24 +261,19 @@ class WallForces:
         # device state: allocated by attach(), never reallocated
         self.rec = self.tables = self.gb = self.partial = self.hist = self.hist_clock = self.origin = None
         self._plan = None
-        self._owner = None                            # the owner's class name once attached - NOT the owner (FieldStats' rule)
         self.N = 0
 
-    start = property(lambda self: self._window[0])
-    stride = property(lambda self: self._window[1])
-    stop = property(lambda self: None if self._window[2] < 0 else self._window[2])
-    enabled = property(lambda self: bool(self._window[3]))
+    start = property(lambda self: self._window.start)
+    stride = property(lambda self: self._window.stride)
+    stop = property(lambda self: self._window.stop)
+    enabled = property(lambda self: self._window.enabled)
 
-    # ---- the owner's side -------------------------------------------------------------------------------------------------------
-    def check_free(self):
-        """Needs no GPU: an owner's constructor calls it before it looks at anything else."""
-        if self._owner is not None:
-            raise ValueError(f"this WallForces is already attached to a {self._owner} (one owner per object: it follows one "
-                             "clock)")
+    # ---- the owner's side (gfv/follow.py) -------------------------------------------------------------------------------------
+    _check_graphs = staticmethod(check_graphs)
 
-    def attach(self, owner, graphs, plan, x_backup):
-        """Called by the owner's constructor with the tensor it advances: fixes the selection, builds the tables and allocates
-        the record and the state (once).  -> self"""
+    def attach(self, owner, graphs, plan, x_backup, clock, clock_word=0):
+        """Called by the owner's constructor with the tensor it advances, its int32 record `clock` and the word of it that counts
+        the fields written: fixes the selection, builds the tables and allocates the record and the state (once).  -> self"""
         self.check_free()
         check_graphs(graphs)
         n = check_field(x_backup)
@@ -296,21 +285,19 @@ class WallForces:
         B = int(plan.B)
         origin = check_origin(self._origin, B)
         t = build_tables(plan, select_faces(graphs, self._faces, self._box))
-        self.rec = torch.zeros(L.WALL_FORCE_RECORD, dtype=torch.int32, device=dev)
         self.gb = torch.zeros((t.Nb, 3, 2), dtype=torch.float64, device=dev)
         self.partial = torch.zeros((t.n_wchunks, L.WALL_FORCE_SUMS), dtype=torch.float64, device=dev)
         self.hist = torch.zeros((self.keep, B, L.WALL_FORCE_SUMS), dtype=torch.float64, device=dev)
         self.hist_clock = torch.zeros(self.keep, dtype=torch.int32, device=dev)
         self.origin = torch.tensor(origin if len(origin) > 1 else origin * B, dtype=torch.float32).to(dev)
-        self.N, self.tables, self._plan = n, t, plan
-        self._write_window()
-        self.reset()
-        self._owner = type(owner).__name__ if not isinstance(owner, str) else owner     # (last: a failed attach leaves it free)
+        self._xb, self._clock, self._clock_ptr = x_backup, clock, clock.data_ptr() + 4 * int(clock_word)
+        self.N, self.tables, self._plan, self.rec = n, t, plan, self._window.attach(dev)
+        self._claim(owner)
         return self
 
-    def launch(self, x_backup, clock_ptr):
+    def launch(self):
         """The two launches, behind the owner's advance: part of the step body (eager steps and recorded lists carry them alike)."""
-        pl, t, lib, st = self._plan, self.tables, L.load(), L.stream_ptr()
+        pl, t, lib, st, x_backup, clock_ptr = self._plan, self.tables, L.load(), L.stream_ptr(), self._xb, self._clock_ptr
         L.check(lib.gfv_wall_force_grad(x_backup.data_ptr(), pl.uvp_dim.data_ptr(), pl.batch.data_ptr(), pl.x_rowptr.data_ptr(),
                                         pl.x_out.data_ptr(), pl.x_B.data_ptr(), pl.An.data_ptr(), pl.rn.data_ptr(),
                                         t.bnode.data_ptr(), t.Nb, int(pl.M), clock_ptr, self.rec.data_ptr(), self.gb.data_ptr(), st),
@@ -322,38 +309,20 @@ class WallForces:
                                        clock_ptr, self.rec.data_ptr(), self.partial.data_ptr(), self.hist.data_ptr(),
                                        self.hist_clock.data_ptr(), self.keep, st), "gfv_wall_force_sum")
 
-    def _need(self):
-        if self.rec is None:
-            raise RuntimeError("this WallForces is not attached yet: hand it to Rollout(..., wall_forces=) or "
-                               "MarchStep(..., wall_forces=)")
-
-    # ---- the record's host-written words ---------------------------------------------------------------------------------------
-    def _write_window(self):
-        w = self._window
-        self.rec[START:STOP + 1].copy_(torch.tensor(w[0:3], dtype=torch.int32))
-        self.rec[ENABLED:ENABLED + 1].copy_(torch.tensor(w[3:4], dtype=torch.int32))
-
     def set_window(self, start=None, stride=None, stop=UNCHANGED, enabled=None):
-        """A new window (None: unchanged; `stop=None` removes the end, leaving `stop` out keeps it), checked before anything
-        changes.  It reaches recorded lists through the device record: nothing is recorded again.  It holds from the next step
-        issued.  The history so far stays: reset() starts over."""
-        w = self._window
-        self._window = check_field_stats_args(w[0] if start is None else start, w[1] if stride is None else stride,
-                                              self.stop if stop is UNCHANGED else stop, bool(w[3]) if enabled is None else enabled)
-        if self.rec is not None:
-            self._write_window()
+        """`Window.set`: a new window under recorded lists.  The history so far stays: reset() starts over."""
+        self._window.set(start, stride, stop, enabled)
 
     def reset(self):
-        """Start over: last = -1, n = 0, in stream order (the ring needs no clearing: rows are read up to n).  The owner's reset()
-        calls it; called alone, the next launch finds a clock it has not seen and samples it if the window holds."""
+        """`Window.reset`, in stream order; the owner's reset() calls it.  The ring needs no clearing (rows are read up to n)."""
         self._need()
-        self.rec[LAST:N_SAMPLES + 1].copy_(torch.tensor([-1, 0], dtype=torch.int32))
+        self._window.reset()
 
     # ---- reading (each of these is one synchronisation) ----------------------------------------------------------------------
     def count(self):
         """Samples taken so far."""
         self._need()
-        return int(self.rec[N_SAMPLES:N_SAMPLES + 1].cpu()[0])
+        return self._window.count()
 
     def raw(self):
         """(record [8] int32, hist [keep, B, 6] float64, hist_clock [keep] int32) as CPU copies (one synchronisation)."""
@@ -407,9 +376,9 @@ def evaluate(graphs, field, faces=None, box=None, origin=(0.0, 0.0)):
         raise ValueError(f"evaluate: field has {int(field.shape[0])} rows, the graphs {plan.N} nodes")
     xb = torch.zeros((plan.N, 12), dtype=torch.float32, device=field.device)
     xb[:, 0:3] = field[:, 0:3].to(torch.float32)
-    wf = WallForces(faces=faces, box=box, origin=origin, start=1, keep=1).attach("evaluate", graphs, plan, xb)
     clock = torch.ones(1, dtype=torch.int32, device=field.device)
-    wf.launch(xb, clock.data_ptr())
+    wf = WallForces(faces=faces, box=box, origin=origin, start=1, keep=1).attach("evaluate", graphs, plan, xb, clock)
+    wf.launch()
     rec, hist, _ = wf.raw()
     assert int(rec[N_SAMPLES]) == 1
     return hist[0]

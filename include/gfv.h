@@ -1039,13 +1039,11 @@ int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
                       int32_t max_inner, int32_t min_inner, float* snap, int32_t keep, int32_t* mirror_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Field statistics (gfv/fieldstats.py, DESIGN.md 5t): the time mean, the variances, the Reynolds shear stress u'v' and the
- * extremes of the node field over a window of a run, kept on the device.  ONE launch behind the launch that has advanced the
- * field (gfv_rollout_advance, gfv_march_advance), on the same stream.
- *   x_backup   [N, 12] float, 16-byte aligned: columns 0:3 of a row are the field (u, v, p); nothing else of a row is used
+ * The sampling window (gfv/window.py, csrc/gfv_window.h): which fields of a run the launches that sample it from
+ * behind its advance launch take - gfv_field_stats_update; gfv_wall_force_grad and gfv_wall_force_sum.
  *   clock      the device address of one int32 that increases whenever a new field has been written: word 0 of
  *              gfv_rollout_advance's state, word [6] `level` of gfv_march_advance's record (the idea of GFV_SCHED_FOLLOW)
- *   rec        GFV_FIELD_STATS_RECORD 32-bit words of the caller's:
+ *   rec        GFV_WINDOW_RECORD 32-bit words of the caller's, one record per sampler:
  *     [0] start    (int32, host)    the first clock value to sample
  *     [1] stride   (int32, host)    sampling stride; values < 1 are read as 1
  *     [2] stop     (int32, host)    exclusive end; negative: none
@@ -1054,25 +1052,37 @@ int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
  *     [5]          (int32)          arrival counter, zero between launches
  *     [6] enabled  (int32, host)    0 pauses sampling
  *     [7]                           zero
+ * The rule, with rec and *clock AS THE LAUNCH FINDS THEM (every thread reads them before anything is written; the workgroup that
+ * arrives last - of a sampler's last launch - writes the record, so the launches of one sampler decide alike):
+ *   c = *clock
+ *   take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % max(stride, 1) == 0
+ *   take false:  nothing of the sampler's state is read or written
+ *   take true:   the sampler's own rule, below
+ *   then, always:  last = c if it differs;  n += 1 if take;  the counter back to 0
+ * So a reset is last = -1, n = 0.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_WINDOW_RECORD 8
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Field statistics (gfv/fieldstats.py, DESIGN.md 5t): the time mean, the variances, the Reynolds shear stress u'v' and the
+ * extremes of the node field over a window of a run, kept on the device.  ONE launch behind the launch that has advanced the
+ * field (gfv_rollout_advance, gfv_march_advance), on the same stream.
+ *   x_backup   [N, 12] float, 16-byte aligned: columns 0:3 of a row are the field (u, v, p); nothing else of a row is used
+ *   clock, rec the clock and the window's record (GFV_WINDOW_RECORD, above)
  *   sums       double [GFV_FIELD_STATS_SUMS, N], planar: S1u, S1v, S1p, S2uu, S2vv, S2pp, S2uv
  *   aux        float [GFV_FIELD_STATS_AUX, N], planar: the shift K of u, v, p; the minimum of u, v, p; the maximum of u, v, p
- * The rule, with the record AS THE LAUNCH FINDS IT (every workgroup reads it and *clock before anything is written; the
- * workgroup that arrives last writes it):
- *   c = *clock
- *   take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % stride == 0
- *   take false:  no row and no element of sums or aux is read or written
- *   take true, per row, x the row's three floats:
- *     n == 0:    K = min = max = x; all seven sums are written as +0.0 (so a reset is last = -1, n = 0: no memset)
+ * The rule: the window's (take false: no row and no element of sums or aux is read or written), and with take true, per row, x
+ * the row's three floats:
+ *     n == 0:    K = min = max = x; all seven sums are written as +0.0 (so a reset needs no memset)
  *     n > 0:     d = (double)x - (double)K per channel; S1 += d; S2uu += du * du; S2vv += dv * dv; S2pp += dp * dp;
  *                S2uv += du * dv - each product and each sum ONE IEEE double operation, nothing contracted;
  *                min = fminf(min, x); max = fmaxf(max, x) (a NaN sample leaves them; a NaN they hold is replaced)
- *   then:        last = c if it differs; n += 1 if take; the counter back to 0
  * So mean = K + S1 / n, the population variance S2 / n - (S1 / n)^2, cov(u, v) = S2uv / n - (S1u / n)(S1v / n): shifted by the
  * first sample, the sums stay of the size of the fluctuation.  No floating-point atomics and no sum across rows: the same
  * inputs give the same bits, whatever the grid.
  * GFV_ERR_ARG (nothing launched) on a NULL pointer, N < 1 or an x_backup that is not 16-byte aligned.
  * ---------------------------------------------------------------------------------------------------------- */
-#define GFV_FIELD_STATS_RECORD 8
+#define GFV_FIELD_STATS_RECORD 8 /* = GFV_WINDOW_RECORD */
 #define GFV_FIELD_STATS_SUMS 7
 #define GFV_FIELD_STATS_AUX 9
 int gfv_field_stats_update(const float* x_backup, int32_t N, const int32_t* clock, int32_t* rec, double* sums, float* aux,
@@ -1229,7 +1239,8 @@ int gfv_step_control_rows(const float* x_backup, const int32_t* batch, const flo
  * per graph, for the field a run has just written - the momentum flux the residual itself attributes to the wall faces (P_flux -
  * vis_flux of FVscheme.py:203-229; the convective flux is left out: it is zero on a wall whose velocity has no normal component).
  * TWO launches behind the launch that has advanced the field (gfv_rollout_advance, gfv_march_advance), on the same stream:
- * gfv_wall_force_grad, then gfv_wall_force_sum.  `x_backup`, `clock` and the words of `rec` are gfv_field_stats_update's.
+ * gfv_wall_force_grad, then gfv_wall_force_sum.  `x_backup` is gfv_field_stats_update's; `clock` and `rec` are the clock and the
+ * window's record (GFV_WINDOW_RECORD, above).
  *   uvp_dim float [B, 3];  batch int32 [N];  theta float [B, ld_theta], ld_theta >= 5: columns 3 and 4 are read at every launch
  *   x_rowptr int32 [N + 1], x_out int32 [S], x_B float [S, terms], An float [N, terms * terms], rn float [N, terms]: the WLSQ
  *              stencil of the plan, as gfv_wlsq_fwd_ex takes it;  terms 2 / 5 / 9 / 14
@@ -1245,9 +1256,7 @@ int gfv_step_control_rows(const float* x_backup, const int32_t* batch, const flo
  *   partial    double [n_wchunks, GFV_WALL_FORCE_SUMS]: workspace
  *   hist       double [keep, B, GFV_WALL_FORCE_SUMS]: (Fp_x, Fp_y, Fv_x, Fv_y, Mp, Mv) per graph, row n % keep
  *   hist_clock int32 [keep]: the clock of a row
- * The rule, with rec and *clock AS EACH LAUNCH FINDS THEM (every thread reads them before anything is written; only the last
- * arriver of the second launch writes rec, so the pair decides alike):
- *   c = *clock;  take = enabled && c != last && c >= start && (stop < 0 || c < stop) && (c - start) % max(stride, 1) == 0
+ * The rule: the window's, each launch with rec and *clock as it finds them (only the last arriver of the second launch writes rec).
  *   take false:  the first launch reads and writes nothing; the second moves no word of partial, hist or hist_clock
  *   take true:
  *     phi_c(i) = x_backup[i, c] / uvp_dim[3 batch[i] + c], c = u, v, p: ONE fp32 division (gfv_step_control_rate's convention)
@@ -1268,12 +1277,11 @@ int gfv_step_control_rows(const float* x_backup, const int32_t* batch, const flo
  *     lane sums fold by the xor butterfly 32, 16, ... 1; per graph, by the workgroup that arrives last: lane l adds the chunk
  *     sums c0 + l, c0 + l + 64, ... in ascending order, then the same butterfly (csrc/gfv_reduce.h states the order)
  *     hist[n % keep, b, :] = the graph's six sums (zero for a graph without a face);  hist_clock[n % keep] = c
- *   then, always:  last = c if it differs;  n += 1 if take;  the counter back to 0
  * No floating-point atomics and no sum across graphs: the same inputs give the same bits, whatever the grid.
  * GFV_ERR_ARG (nothing launched) on a NULL pointer, Nb, Nf, n_wchunks, B or keep < 1, ld_theta < 5, terms outside the four
  * values, an x_backup or wface that is not 16-byte aligned, or a gb, partial or hist that is not 8-byte aligned.
  * ---------------------------------------------------------------------------------------------------------- */
-#define GFV_WALL_FORCE_RECORD 8
+#define GFV_WALL_FORCE_RECORD 8 /* = GFV_WINDOW_RECORD */
 #define GFV_WALL_FORCE_SUMS 6
 #define GFV_WALL_FORCE_CHUNK 64
 int gfv_wall_force_grad(const float* x_backup, const float* uvp_dim, const int32_t* batch, const int32_t* x_rowptr,

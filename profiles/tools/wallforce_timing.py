@@ -110,7 +110,7 @@ def main():
     xb = legs["plain"].x_backup.clone()
     n_launch = LAUNCH_BLOCK + 20
     clocks = torch.arange(1, 2 * n_launch + 1, dtype=torch.int32, device=dev)
-    lone = WallForces(box=box, origin=ORIGIN, keep=16).attach("wallforce_timing", graphs(), pl, xb)
+    lone = WallForces(box=box, origin=ORIGIN, keep=16).attach("wallforce_timing", graphs(), pl, xb, clocks)
     lt = lone.tables
 
     def grad(i):

@@ -6,16 +6,11 @@ the extremes.  Nothing here touches a GPU.
 """
 import numpy as np
 
-START, STRIDE, STOP, LAST, N, COUNTER, ENABLED = range(7)
-RECORD, SUMS, AUX = 8, 7, 9
+from window_ref import COUNTER, ENABLED, LAST, N, RECORD, START, STOP, STRIDE, commit, take  # noqa: F401  (the window: once)
+
+SUMS, AUX = 7, 9
 
 f32, f64 = np.float32, np.float64
-
-
-def take(rec, c):
-    """Whether a launch that finds the record `rec` and the clock value `c` samples."""
-    start, stride, stop = int(rec[START]), max(int(rec[STRIDE]), 1), int(rec[STOP])
-    return bool(rec[ENABLED] != 0 and c != int(rec[LAST]) and c >= start and (stop < 0 or c < stop) and (c - start) % stride == 0)
 
 
 class FieldStatsRef:
@@ -50,11 +45,7 @@ class FieldStatsRef:
                     self.sums[6] = self.sums[6] + d[0] * d[1]
                     self.aux[3:6] = np.fmin(self.aux[3:6], x)
                     self.aux[6:9] = np.fmax(self.aux[6:9], x)
-        if c != int(self.rec[LAST]):
-            self.rec[LAST] = c
-        if taken:
-            self.rec[N] += 1
-        self.rec[COUNTER] = 0
+        commit(self.rec, c, taken)
         return taken
 
     def moments(self):

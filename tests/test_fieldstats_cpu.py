@@ -141,7 +141,7 @@ def test_argument_refusals_need_no_device():
     with pytest.raises(ValueError, match="GPU"):
         check_field(torch.zeros(4, 12))                                     # a CPU tensor
     with pytest.raises(ValueError, match="GPU"):
-        FieldStats().attach(object(), torch.zeros(4, 12))
+        FieldStats().attach(object(), torch.zeros(4, 12), torch.zeros(1, dtype=torch.int32))
     # the owners
     check_field_stats(None, 3)
     check_field_stats(FieldStats(), 0)

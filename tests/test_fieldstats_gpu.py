@@ -342,7 +342,7 @@ def test_refusals():
         Rollout(model, _graphs("poly"), max_steps=0, field_stats=fs)
     fs.check_free()                                                                    # a constructor that raised attached nothing
     with pytest.raises(ValueError, match="GPU"):
-        FieldStats().attach(object(), torch.zeros(8, 12))                             # a CPU tensor
+        FieldStats().attach(object(), torch.zeros(8, 12), torch.zeros(1, dtype=torch.int32))     # a CPU tensor
     with pytest.raises(ValueError, match="FieldStats"):
         Rollout(model, _graphs("poly"), max_steps=4, field_stats=dict(start=1))
     r = Rollout(model, _graphs("poly"), max_steps=4, launch_mode="eager", field_stats=fs)

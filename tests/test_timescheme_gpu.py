@@ -431,7 +431,7 @@ def test_with_time_bc_and_field_stats_the_order_of_the_launches_does_not_matter(
         def _follow_level(self):
             self.time_scheme.launch()
             self.time_bc.launch()
-            self.field_stats.launch(self.x_backup, self._march.data_ptr() + 4 * 6)      # (word [6]: the level count)
+            self.field_stats.launch()
 
     outs = []
     for cls in (MarchStep, Reversed):

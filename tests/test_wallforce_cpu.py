@@ -168,7 +168,7 @@ def test_refusals_and_window_arguments():
         with pytest.raises(RuntimeError, match="not attached"):
             call()
     with pytest.raises(ValueError, match="GPU"):
-        wf.attach(object(), graphs, plan, torch.zeros(plan.N, 12))                                 # a CPU tensor
+        wf.attach(object(), graphs, plan, torch.zeros(plan.N, 12), torch.zeros(1, dtype=torch.int32))     # a CPU tensor
     wf.check_free()
     assert wf.rec is None and wf.tables is None
     for kw in (dict(ref_length=0.0), dict(ref_length=0.1, ref_speed=-1.0), dict(ref_length="1")):

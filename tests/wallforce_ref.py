@@ -10,8 +10,9 @@ import math
 
 import numpy as np
 
-START, STRIDE, STOP, LAST, N, COUNTER, ENABLED = range(7)
-RECORD, SUMS, CHUNK = 8, 6, 64
+from window_ref import COUNTER, ENABLED, LAST, N, RECORD, START, STOP, STRIDE, commit, take  # noqa: F401  (the window: once)
+
+SUMS, CHUNK = 6, 64
 WALL_BOUNDARY = 3
 
 f32, f64 = np.float32, np.float64
@@ -185,12 +186,6 @@ def graph_sums(m, wface, origin, field, gb):
 
 
 # ---- the record and the ring --------------------------------------------------------------------------------------------------------
-def take(rec, c):
-    """Whether a pair of launches that finds the record `rec` and the clock value `c` samples (gfv_field_stats_update's rule)."""
-    start, stride, stop = int(rec[START]), max(int(rec[STRIDE]), 1), int(rec[STOP])
-    return bool(rec[ENABLED] != 0 and c != int(rec[LAST]) and c >= start and (stop < 0 or c < stop) and (c - start) % stride == 0)
-
-
 class WallForcesRef:
     """The record and the ring a sequence of launch pairs works on, and `launch()`: one pair applied to them."""
 
@@ -218,11 +213,7 @@ class WallForcesRef:
             row = int(self.rec[N]) % self.keep
             self.hist[row], self.mag[row] = graph_sums(self.m, self.t["wface"], self.origin, field, gb)
             self.hist_clock[row] = c
-        if c != int(self.rec[LAST]):
-            self.rec[LAST] = c
-        if taken:
-            self.rec[N] += 1
-        self.rec[COUNTER] = 0
+        commit(self.rec, c, taken)
         return taken
 
     def rows(self):
