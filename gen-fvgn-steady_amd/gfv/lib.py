@@ -123,6 +123,8 @@ TIME_SCHEME_RECORD, TIME_SCHEME_BDF1, TIME_SCHEME_BDF2 = 4, 1, 2
 STEP_CONTROL_RECORD, STEP_CONTROL_PARAMS, STEP_CONTROL_STATE = 4, 8, 4
 # GFV_WALL_FORCE_* of include/gfv.h: words of the record (the window's), sums per graph, faces per chunk at most
 WALL_FORCE_RECORD, WALL_FORCE_SUMS, WALL_FORCE_CHUNK = WINDOW_RECORD, 6, 64
+# GFV_PROBE_* of include/gfv.h: words of the record (the window's), doubles per probe and sample
+PROBE_RECORD, PROBE_SUMS = WINDOW_RECORD, 9
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -311,6 +313,7 @@ _SIGNATURES = {
     "gfv_wall_force_grad": (C.c_int, [C.c_void_p] * 9 + [C.c_int32, C.c_int32] + [C.c_void_p] * 4),
     "gfv_wall_force_sum": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p] * 7
                            + [C.c_int32, C.c_void_p]),
+    "gfv_probe_sample": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -1040,7 +1040,7 @@ int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
 
 /* ------------------------------------------------------------------------------------------------------------
  * The sampling window (gfv/window.py, csrc/gfv_window.h): which fields of a run the launches that sample it from
- * behind its advance launch take - gfv_field_stats_update; gfv_wall_force_grad and gfv_wall_force_sum.
+ * behind its advance launch take - gfv_field_stats_update; gfv_wall_force_grad and gfv_wall_force_sum; gfv_probe_sample.
  *   clock      the device address of one int32 that increases whenever a new field has been written: word 0 of
  *              gfv_rollout_advance's state, word [6] `level` of gfv_march_advance's record (the idea of GFV_SCHED_FOLLOW)
  *   rec        GFV_WINDOW_RECORD 32-bit words of the caller's, one record per sampler:
@@ -1292,6 +1292,57 @@ int gfv_wall_force_sum(const float* x_backup, const float* uvp_dim, const float*
                        const int32_t* wchunk_beg, const int32_t* wchunk_end, const int32_t* gwchunk_ptr, int32_t n_wchunks,
                        int32_t Nf, int32_t B, const float* origin, const double* gb, const int32_t* clock, int32_t* rec,
                        double* partial, double* hist, int32_t* hist_clock, int32_t keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Probes (gfv/probes.py): the value and the gradient of (u, v, p) at fixed points of the mesh, for the field a run
+ * has just written.  ONE launch behind the launch that has advanced the field (gfv_rollout_advance, gfv_march_advance), on the same
+ * stream.  `x_backup`, `uvp_dim` and `batch` are gfv_wall_force_grad's; `clock` and `rec` are the clock and the window's record
+ * (GFV_WINDOW_RECORD, above).
+ *
+ * What a probe is (fixed when the tables are built, on the host, in float64; nothing of it is done by the launch).
+ *   units      phi_c(n) = x_backup[n, c] / uvp_dim[3 batch[n] + c], c = u, v, p: ONE fp32 division, then double
+ *   location   a probe is a point x (double) and the graph b it lies in.  Over the cells C of graph b (gcell_ptr[b] ..
+ *              gcell_ptr[b + 1] - 1), with the incidences k = crow[C] .. crow[C + 1] - 1 of a cell, its outward face vectors kS[k]
+ *              and the stored face centres fpos[kface[k]] (fp32 data, every operation in double):
+ *                  d(C) = max_k ((x - fpos[kface[k]]) . kS[k]) / |kS[k]|
+ *              the signed distance by which x lies outside the cell's farthest face line; d <= 0 exactly inside a CONVEX cell
+ *              (cells are taken as convex).  The probe's cell is the cell of least d, the lowest index among equals (a point at
+ *              an interior face's stored centre has d = 0 exactly in both neighbours).  outside = d_min / sqrt(area[cell]); a
+ *              probe with outside > tolerance is refused, an accepted one is not moved.
+ *   value      the cell's vertices are V = knode[crow[C] .. crow[C + 1] - 1], k of them; g_v[c] is the WLSQ gradient of phi_c at
+ *              vertex v - the first two entries of the solution of the row-normalised system of gfv_wall_force_grad, any of the
+ *              four orders.  The scheme's own second-order reconstruction (node value plus gradient times offset, the ends
+ *              averaged, as gfv_face_fwd forms a face value from two ends), over the k vertices with EQUAL weights:
+ *                  value_c(x)    = (1 / k) sum_v ( phi_c(v) + g_v[c] . (x - pos[v]) )
+ *                  gradient_c(x) = (1 / k) sum_v g_v[c]
+ *   weights    both are linear in phi, with the same weights for the three channels.  Per vertex v, with A = An[v] / rn[v] (row
+ *              r divided by rn[v, r]) and z_a the solution of A^T z_a = e_a, a = 0, 1: stencil entry s = x_rowptr[v] ..
+ *              x_rowptr[v + 1] - 1 adds t_a = (z_a . (x_B[s] / rn[v])) / k to the d/dx_a weight of node x_out[s] and -t_a to that
+ *              of v; the value weight is 1 / k on v, plus (x - pos[v]) . (the two gradient weights) on every node they touch.
+ *              Entries of one node are merged (a node reached through several vertices' stencils, a stencil that names a node
+ *              twice), in a fixed order.
+ *   pw_ptr     int32 [P + 1]: the entries of probe p are pw_ptr[p] .. pw_ptr[p + 1] - 1 (a probe may have none: its row is zero)
+ *   pw_node    int32 [nnz]: the nodes, ascending and unique within a probe
+ *   pw_w       double [nnz, 3], 8-byte aligned: (value weight, d/dx weight, d/dy weight)
+ *   hist       double [keep, P, GFV_PROBE_SUMS], 8-byte aligned: row n % keep; of probe p the nine doubles q = 3 c + j,
+ *              j = 0 the value, 1 d/dx, 2 d/dy of channel c
+ *   hist_clock int32 [keep]: the clock of a row
+ * The rule: the window's, with rec and *clock as the launch finds them.
+ *   take false:  no word of hist or hist_clock moves
+ *   take true:   one wave per probe; lane l takes the entries e = pw_ptr[p] + l, + l + 64, ... in ascending order and, starting
+ *                from +0.0, adds pw_w[e, j] * phi_c(pw_node[e]) into nine doubles - each product and each sum ONE IEEE double
+ *                operation, nothing contracted; the 64 lane sums fold by the xor butterfly 32, 16, ... 1 (csrc/gfv_reduce.h);
+ *                hist[n % keep, p, q] = the sum;  hist_clock[n % keep] = c
+ * No floating-point atomics, nothing handed between workgroups, an order that does not depend on the grid: the same inputs give
+ * the same bits.  Nothing but hist, hist_clock and rec is written.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer, P < 1, keep < 1, an x_backup that is not 16-byte aligned, or a pw_w or hist
+ * that is not 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_PROBE_RECORD 8 /* = GFV_WINDOW_RECORD */
+#define GFV_PROBE_SUMS 9
+int gfv_probe_sample(const float* x_backup, const float* uvp_dim, const int32_t* batch, const int32_t* pw_ptr,
+                     const int32_t* pw_node, const double* pw_w, int32_t P, const int32_t* clock, int32_t* rec, double* hist,
+                     int32_t* hist_clock, int32_t keep, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
