@@ -116,13 +116,15 @@ static __device__ __forceinline__ bool gfv_arrive_last_nodata(int* counter) {
 }
 
 // The last arriver's fold of K sums per chunk (partial [n_chunks, K]): lane l takes chunks c0 + l, c0 + l + 64, ... < c1 in
-// ascending order into s[K].  The caller folds the 64 lanes (gfv_wave_sum, or Anderson's tree in LDS).
-template <int K>
+// ascending order into s[K].  The caller folds the 64 lanes (gfv_wave_sum, or Anderson's tree in LDS).  LD: the doubles of a
+// chunk's row where it holds more than the K sums (the flow integrals' two maxima behind their ten sums).
+template <int K, int LD = K>
 static __device__ __forceinline__ void gfv_fold_chunks(const double* partial, int c0, int c1, int lane, double (&s)[K]) {
+  static_assert(LD >= K, "a row holds its K sums");
 #pragma unroll
   for (int k = 0; k < K; ++k) s[k] = 0.0;
   for (int q = c0 + lane; q < c1; q += 64) {
-    const double* p = partial + (size_t)K * q;
+    const double* p = partial + (size_t)LD * q;
 #pragma unroll
     for (int k = 0; k < K; ++k) s[k] += gfv_ld_agent(p + k);
   }

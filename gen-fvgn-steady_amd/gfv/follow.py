@@ -1,11 +1,11 @@
 """Followers of a run's clock: what the five followers - `FieldStats`, `WallForces`, `Probes`, `TimeBC` and `TimeScheme` - share
-(DESIGN.md 5l).
+(DESIGN.md 5l), and a sixth, `FlowIntegrals` (keyword `integrals`), with them.
 
 A follower is handed to an owner (`Rollout`, `MarchStep`; `TrainStep` for a `TimeScheme`) by keyword; its launches sit behind the
 owner's advance launch, in the step body, and read a clock word that launch writes.  The protocol: the owner's constructor calls
 `check_followers` before it touches a device and each follower's own `attach(owner, ...)` LAST; `attach` binds the clock (the
 owner's int32 record and the word of it that counts the fields written: the tensor is kept alive, the word's address stored), so
-`launch()` and `reset()` take no argument; the owner keeps its followers in `_followers`, in the order field_stats, wall_forces,
+`launch()` and `reset()` take no argument; the owner keeps its followers in `_followers`, in the order field_stats, wall_forces, integrals,
 probes, time_bc, time_scheme, and loops over it in its step body and in its `reset()`.  One owner per follower.  A follower holds NO strong
 reference to its owner, only the owner's class name (a reference back would tie the two into a cycle and keep the owner's recorded
 lists, and a MarchStep's pinned mirror, alive until a garbage collection), and the claim is `attach`'s last statement: an attach
@@ -54,9 +54,10 @@ class Follower:
             obj._check_graphs(graphs)
 
 
-def check_followers(who, graphs, anderson, field_stats=None, wall_forces=None, time_bc=None, time_scheme=None, probes=None):
+def check_followers(who, graphs, anderson, field_stats=None, wall_forces=None, time_bc=None, time_scheme=None, integrals=None,
+                    probes=None):
     """An owner's one check of the followers it is handed, before any device is touched; the order is the launch order."""
-    from . import fieldstats as F, probes as P, timebc as B, timescheme as S, wallforce as W
-    for cls, obj in ((F.FieldStats, field_stats), (W.WallForces, wall_forces), (P.Probes, probes), (B.TimeBC, time_bc),
-                     (S.TimeScheme, time_scheme)):
+    from . import fieldstats as F, integrals as I, probes as P, timebc as B, timescheme as S, wallforce as W
+    for cls, obj in ((F.FieldStats, field_stats), (W.WallForces, wall_forces), (I.FlowIntegrals, integrals), (P.Probes, probes),
+                     (B.TimeBC, time_bc), (S.TimeScheme, time_scheme)):
         cls.check_handed(who, obj, graphs, anderson)

@@ -125,6 +125,8 @@ STEP_CONTROL_RECORD, STEP_CONTROL_PARAMS, STEP_CONTROL_STATE = 4, 8, 4
 WALL_FORCE_RECORD, WALL_FORCE_SUMS, WALL_FORCE_CHUNK = WINDOW_RECORD, 6, 64
 # GFV_PROBE_* of include/gfv.h: words of the record (the window's), doubles per probe and sample
 PROBE_RECORD, PROBE_SUMS = WINDOW_RECORD, 9
+# GFV_FLOW_* of include/gfv.h: words of the record (the window's), summed and maximised columns per graph, cells per chunk at most
+FLOW_RECORD, FLOW_SUMS, FLOW_MAXS, FLOW_CHUNK = WINDOW_RECORD, 10, 2, 64
 # GFV_SCHED_* of include/gfv.h: doubles of a schedule record, milestones at most, the modes and the kinds of gfv_lr_schedule
 SCHED_RECORD, SCHED_MAX_MILESTONES = 32, 8
 SCHED_EVAL, SCHED_TICK, SCHED_FOLLOW = 0, 1, 2
@@ -314,6 +316,7 @@ _SIGNATURES = {
     "gfv_wall_force_sum": (C.c_int, [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 9 + [C.c_int32] * 3 + [C.c_void_p] * 7
                            + [C.c_int32, C.c_void_p]),
     "gfv_probe_sample": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_void_p]),
+    "gfv_flow_integrals": (C.c_int, [C.c_void_p] * 13 + [C.c_int32] * 3 + [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p]),
     "gfv_lr_schedule": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "gfv_loss_balance": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -59,6 +59,13 @@ Allowed beside every other follower (`StepControl` included: the time of a sampl
 `step_history()`); refused for graphs of a DevicePool.  Not part of `state_dict()`.  `probes=None` (the default) issues no new
 launch and allocates nothing.
 
+`integrals=FlowIntegrals(start=, stride=, stop=, keep=, fields=)` (gfv/integrals.py): one more launch behind the march
+launch, after the wall-force pair and before the probes, sums per graph the kinetic energy, the enstrophy, the norms of the discrete
+divergence and the flux through the inflow, outflow and other boundary faces for every COMPLETED level - one row of a device ring
+per level, whatever its inner count; held steps add nothing.  `ms.integrals.read()` reads them.  Allowed beside every other follower
+(`StepControl` included: the time of a sample is joined through its clock with `step_history()`); refused for graphs of a DevicePool.
+Not part of `state_dict()`.  `integrals=None` (the default) issues no new launch and allocates nothing.
+
 `time_bc=TimeBC(velocity=, source=, nodes=)` (gfv/timebc.py): one more launch behind the march launch rewrites the
 Dirichlet velocity targets and the source coefficient for the level about to be computed (level count + 1), from per-graph waveform
 records on the device.  The host cannot do this: only the device knows which step starts a new level.  Inner iterations and held
@@ -175,14 +182,14 @@ def decode_history(words, B):
 class MarchStep(TrainStep):
     def __init__(self, model, graphs, *, max_inner=20, min_inner=1, tol=1e-2, abs_tol=None, max_levels=1000, keep=0,
                  use_graph="list", field_stats=None, time_bc=None, time_scheme=None, wall_forces=None, probes=None,
-                 **trainstep_kwargs):
+                 integrals=None, **trainstep_kwargs):
         args = check_march_args(max_inner, min_inner, tol, abs_tol, max_levels, keep)
         check_step_args(use_graph, trainstep_kwargs)
         check_adapt_owner("MarchStep", time_scheme, time_bc, field_stats)
         check_followers("MarchStep", graphs, 0, field_stats=field_stats, wall_forces=wall_forces, time_bc=time_bc,
-                        time_scheme=time_scheme, probes=probes)
+                        time_scheme=time_scheme, integrals=integrals, probes=probes)
         self._march = None
-        self.field_stats = self.wall_forces = self.probes = self.time_bc = None
+        self.field_stats = self.wall_forces = self.integrals = self.probes = self.time_bc = None
         self._followers = []
         super().__init__(model, graphs, use_graph=use_graph, **trainstep_kwargs)
         self._max_inner, self._min_inner, self._tol, self._abs_tol, self.max_levels, self.keep = args
@@ -207,15 +214,16 @@ class MarchStep(TrainStep):
         # sample nothing, and time_bc (the targets of level count + 1) and time_scheme (the ring's rotation, the next level's baseline)
         # write the same bits again (an early-out would need the blocks to agree on a "last" word: DESIGN.md 5u); the attach of each
         # of those two issues its launch for level 0 (the level count is 0; second order with `previous=`).  They touch disjoint data
-        # (wall_forces and probes read x_backup and the plan) and none reads what another writes: their order among themselves does
+        # (wall_forces, integrals and probes read x_backup and the plan) and none reads what another writes: their order among themselves does
         # not matter.
         self.field_stats = field_stats and field_stats.attach(self, self.x_backup, self._march, LEVEL)
         self.wall_forces = wall_forces and wall_forces.attach(self, graphs, pl, self.x_backup, self._march, LEVEL)
+        self.integrals = integrals and integrals.attach(self, graphs, pl, self.x_backup, self._march, LEVEL)
         self.probes = probes and probes.attach(self, graphs, pl, self.x_backup, self._march, LEVEL)
         self.time_bc = time_bc and time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._march, LEVEL, self.max_levels)
         self.time_scheme = time_scheme and time_scheme.attach(self, pl, self.x_backup, self._march, LEVEL)
-        self._followers = [f for f in (self.field_stats, self.wall_forces, self.probes, self.time_bc, self.time_scheme)
-                           if f is not None]
+        self._followers = [f for f in (self.field_stats, self.wall_forces, self.integrals, self.probes, self.time_bc,
+                                       self.time_scheme) if f is not None]
 
     def __del__(self):
         host = getattr(self, "_mirror", None)

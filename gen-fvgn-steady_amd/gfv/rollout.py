@@ -64,6 +64,15 @@ ring of the last `keep` samples, following the step counter.  Eager steps and re
 one synchronisation, `set_window()` moves the window under a recorded list.  Refused together with `anderson` > 0 (a steady user calls
 `gfv.probes.sample()` on the converged field) and for graphs of a DevicePool; allowed beside every other follower.  `probes=None`
 (the default) issues no new launch and allocates nothing.
+
+Flow integrals (`integrals=FlowIntegrals(start=, stride=, stop=, keep=, fields=)`; gfv/integrals.py).  One more launch
+behind the advance, after the wall-force pair and before the probes, sums per graph the kinetic energy, the enstrophy, the norms of
+the discrete divergence, the circulation, the pressure integral and the flux through the inflow, outflow and other boundary faces of
+the field just written into a device ring of the last `keep` samples, following the step counter; with `fields=True` it also keeps
+the cell vorticity and divergence of the latest sample.  Eager steps and recorded lists carry it alike; `r.integrals.read()` is the
+one synchronisation, `set_window()` moves the window under a recorded list.  Refused together with `anderson` > 0 (a steady user calls
+`gfv.integrals.evaluate()` on the converged field) and for graphs of a DevicePool; allowed beside every other follower.
+`integrals=None` (the default) issues no new launch and allocates nothing.
 """
 from __future__ import annotations
 
@@ -100,12 +109,12 @@ class Rollout:
 
     def __init__(self, model, graphs, max_steps=1000, launch_mode="cmd_list", norm_global=None, anderson=0, anderson_beta=1.0,
                  anderson_reg=1e-10, anderson_restart=10.0, anderson_start=0, field_stats=None, time_bc=None,
-                 wall_forces=None, probes=None):
+                 wall_forces=None, probes=None, integrals=None):
         if launch_mode not in ("cmd_list", "eager"):
             raise ValueError('launch_mode must be "cmd_list" or "eager"')
         aa_args = AA.check_args(anderson, anderson_beta, anderson_reg, anderson_restart, anderson_start)
         check_followers("Rollout", graphs, aa_args[0], field_stats=field_stats, wall_forces=wall_forces, time_bc=time_bc,
-                        probes=probes)
+                        integrals=integrals, probes=probes)
         graph_node = graphs[0]
         x = graph_node.x
         require_gpu(x)
@@ -140,13 +149,15 @@ class Rollout:
         self._outs = None
         self._fwd = StaticForward(model, pl.B, dev)
         # The followers of the step counter (gfv/follow.py; word 0 of _state), attached last: should a line above raise, they stay
-        # free for another owner.  Behind the advance field_stats samples the field just written, wall_forces and probes read it and the
+        # free for another owner.  Behind the advance field_stats samples the field just written, wall_forces, integrals and probes read it and the
         # plan and write only their own state, time_bc writes the targets of step counter + 1 (its attach: those of step 1, the counter is 0).
         self.field_stats = field_stats and field_stats.attach(self, self.x_backup, self._state, 0)
         self.wall_forces = wall_forces and wall_forces.attach(self, graphs, pl, self.x_backup, self._state, 0)
+        self.integrals = integrals and integrals.attach(self, graphs, pl, self.x_backup, self._state, 0)
         self.probes = probes and probes.attach(self, graphs, pl, self.x_backup, self._state, 0)
         self.time_bc = time_bc and time_bc.attach(self, graphs, pl, self.x_backup, self.x, self._state, 0, self.max_steps)
-        self._followers = [f for f in (self.field_stats, self.wall_forces, self.probes, self.time_bc) if f is not None]
+        self._followers = [f for f in (self.field_stats, self.wall_forces, self.integrals, self.probes, self.time_bc)
+                           if f is not None]
 
     # ---- weights -------------------------------------------------------------------------------------------------------
     def refresh_weights(self):

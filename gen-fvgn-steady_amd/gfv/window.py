@@ -1,4 +1,4 @@
-"""The sampling window: which fields of a run a sampler (`FieldStats`, `WallForces`, `Probes`; gfv/follow.py) takes.
+"""The sampling window: which fields of a run a sampler (`FieldStats`, `WallForces`, `FlowIntegrals`, `Probes`; gfv/follow.py) takes.
 
 The clock counts fields written: the field the first step (the first completed level) leaves has clock 1; clock 0 is the initial
 state, which is never sampled (`start` is at least 1).  A clock value is sampled when `start <= clock < stop` and

@@ -1040,7 +1040,8 @@ int gfv_march_advance(const float* uvp_node, float* x_backup, float* x, int32_t 
 
 /* ------------------------------------------------------------------------------------------------------------
  * The sampling window (gfv/window.py, csrc/gfv_window.h): which fields of a run the launches that sample it from
- * behind its advance launch take - gfv_field_stats_update; gfv_wall_force_grad and gfv_wall_force_sum; gfv_probe_sample.
+ * behind its advance launch take - gfv_field_stats_update; gfv_wall_force_grad and gfv_wall_force_sum; gfv_probe_sample;
+ * gfv_flow_integrals.
  *   clock      the device address of one int32 that increases whenever a new field has been written: word 0 of
  *              gfv_rollout_advance's state, word [6] `level` of gfv_march_advance's record (the idea of GFV_SCHED_FOLLOW)
  *   rec        GFV_WINDOW_RECORD 32-bit words of the caller's, one record per sampler:
@@ -1343,6 +1344,67 @@ int gfv_wall_force_sum(const float* x_backup, const float* uvp_dim, const float*
 int gfv_probe_sample(const float* x_backup, const float* uvp_dim, const int32_t* batch, const int32_t* pw_ptr,
                      const int32_t* pw_node, const double* pw_w, int32_t P, const int32_t* clock, int32_t* rec, double* hist,
                      int32_t* hist_clock, int32_t keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Flow integrals (gfv/integrals.py): per graph the area, the kinetic energy, the enstrophy, the L2 and the max norm
+ * of the discrete divergence, the peak vorticity, the circulation, the pressure integral and the flux through the inflow, the
+ * outflow and the other boundary faces, for the field a run has just written; optionally the cell vorticity and the cell
+ * divergence of that field.  ONE launch behind the launch that has advanced the field (gfv_rollout_advance, gfv_march_advance), on
+ * the same stream.  `x_backup` and `uvp_dim` are gfv_wall_force_grad's; `clock` and `rec` are the clock and the window's record
+ * (GFV_WINDOW_RECORD, above).  No gradient and no LU: every quantity is a closed-polygon sum over the plan's incidence tables.
+ *   crow int32 [C + 1], kface, knode int32 [Sg], kS float [Sg, 2]: the (cell, face) incidences of cell C are k = crow[C] ..
+ *              crow[C + 1] - 1; the face, the vertex and the cell's OUTWARD surface vector of incidence k
+ *   es, er int32 [E]: a face's end nodes;  area float [C]: the cells' areas
+ *   btype      int32 [Sg], built once on the host: 0 where the face kface[k] has two incidences; where it has exactly one: 1 if
+ *              its face type is INFLOW (1), 2 if OUTFLOW (2), 3 otherwise
+ *   cchunk_beg, cchunk_end int32 [n_cchunks], gcchunk_ptr int32 [B + 1]: chunks of at most GFV_FLOW_CHUNK consecutive cells that
+ *              never cross a graph, and each graph's range of chunks (the form of a plan's chunk tables)
+ *   partial    double [n_cchunks, GFV_FLOW_SUMS + GFV_FLOW_MAXS], 8-byte aligned: workspace
+ *   hist       double [keep, B, GFV_FLOW_SUMS + GFV_FLOW_MAXS], 8-byte aligned: the twelve columns per graph, row n % keep
+ *   hist_clock int32 [keep]: the clock of a row
+ *   cell_out   double [C, 2], 8-byte aligned, or NULL: (Gamma_C / a, D_C / a), the cell vorticity and the cell divergence
+ * The rule: the window's, with rec and *clock as the launch finds them.
+ *   take false:  no word of partial, hist, hist_clock or cell_out moves
+ *   take true:
+ *     phi_c(i) = x_backup[i, c] / uvp_dim[3 batch[i] + c], c = u, v, p: ONE fp32 division, then double (a cell's nodes lie in the
+ *     cell's graph b, the graph of its chunk: the launch reads uvp_dim[3 b + c]).  Everything below is one IEEE double operation in
+ *     the order written, nothing contracted.
+ *     per cell C with its n incidences k, ascending:  f = kface[k], s = es[f], r = er[f], S = (double)kS[k]
+ *       u_f = 0.5 * (u_s + u_r), v_f likewise            (the trapezoid face value: exact for a linear field; NOT the residual's
+ *                                                         reconstructed face value)
+ *       d_k = u_f * S.x + v_f * S.y                       g_k = v_f * S.x - u_f * S.y
+ *       D_C = sum_k d_k, Gamma_C = sum_k g_k, from +0.0   (the integral of div u over the cell; its circulation, the integral of
+ *                                                         omega = dv/dx - du/dy)
+ *       ubar, vbar, pbar = (sum_k phi(knode[k]), from +0.0) / (double)n;    a = (double)area[C]
+ *     the twelve columns, per cell:
+ *       0 area                a                                    6 pressure . area     pbar * a
+ *       1 kinetic energy      (0.5 * (ubar*ubar + vbar*vbar)) * a  7 inflow flux         sum of d_k over btype[k] == 1, from +0.0
+ *       2 enstrophy           (0.5 * (Gamma_C * Gamma_C)) / a      8 outflow flux        ... btype[k] == 2
+ *       3 div^2               (D_C * D_C) / a                      9 other boundary flux ... btype[k] == 3
+ *       4 net outflow         D_C                                 10 max |div|           fabs(D_C) / a
+ *       5 circulation         Gamma_C                             11 max |vorticity|     fabs(Gamma_C) / a
+ *     columns 0 .. 9 are sums, 10 and 11 maxima by fmax from +0.0 (a NaN is passed over).  With exactly antisymmetric kS across
+ *     every interior face, column 4 = columns 7 + 8 + 9 up to the rounding of the sums.
+ *     cell_out[C] = (Gamma_C / a, D_C / a), where it is not NULL
+ *     per chunk: one wave; lane l takes the cells beg + l, beg + l + 64, ... < min(end, C) in ascending order from +0.0, the 64
+ *     lane values fold by the xor butterfly 32, 16, ... 1 (the maxima by the same exchanges with fmax); per graph, by the workgroup
+ *     that arrives last: lane l takes the chunks c0 + l, c0 + l + 64, ... in ascending order, then the same butterfly
+ *     (csrc/gfv_reduce.h states the order)
+ *     hist[n % keep, b, :] = the graph's twelve columns (zero for a graph without a cell);  hist_clock[n % keep] = c
+ * No floating-point atomics and no sum across graphs: the same inputs give the same bits, whatever the grid.  Nothing but partial,
+ * hist, hist_clock, cell_out and rec is written.
+ * GFV_ERR_ARG (nothing launched) on a NULL pointer other than cell_out, C, B, n_cchunks or keep < 1, an x_backup that is not
+ * 16-byte aligned, or a kS, partial, hist or cell_out that is not 8-byte aligned (a vector kS[k] is read as one pair).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define GFV_FLOW_RECORD 8 /* = GFV_WINDOW_RECORD */
+#define GFV_FLOW_SUMS 10
+#define GFV_FLOW_MAXS 2
+#define GFV_FLOW_CHUNK 64
+int gfv_flow_integrals(const float* x_backup, const float* uvp_dim, const int32_t* crow, const int32_t* kface,
+                       const int32_t* knode, const float* kS, const int32_t* btype, const int32_t* es, const int32_t* er,
+                       const float* area, const int32_t* cchunk_beg, const int32_t* cchunk_end, const int32_t* gcchunk_ptr,
+                       int32_t n_cchunks, int32_t C, int32_t B, const int32_t* clock, int32_t* rec, double* partial, double* hist,
+                       int32_t* hist_clock, int32_t keep, double* cell_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Learning-rate schedules evaluated on the device (gfv/schedule.py; the reference's utils/scheduler.py attached
